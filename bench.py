@@ -20,8 +20,13 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line: whole-job samples/sec (aggregate over ranks),
-plus effective gather + remote-read GB/s in ``extra``.
+Rank 0 prints ONE JSON line: whole-job samples/sec (aggregate over ranks)
+and ``ms_per_step``. A plain run does nothing beyond setup, warmup and the
+timed steps; ``--full`` adds the measured local/remote traffic (remote-read
+GB/s, true CSR bytes) and the store counters to ``extra``.
+``--dump-outputs DIR`` writes the last timed step's outputs as .npy files;
+shard contents, model weights and index order are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -60,7 +65,49 @@ def parse_args():
                    help="torch.distributed backend override (default: nccl on "
                         "GPU, gloo on CPU; gloo also works on GPU for "
                         "oversubscribed single-GPU testing)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step "
+                        "returned to its caller as DIR/<name>.npy (float32/"
+                        "float64; outputs above the size cap are a fixed, "
+                        "seeded sample). Rank 0 writes.")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements: exact per-owner "
+                        "local/remote traffic of the timed indices (remote-read "
+                        "GB/s, true CSR bytes) and the store's own counters")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
+
+
+# --dump-outputs: each array is capped at 6 Mi elements (24 MB as float32, 48 MB
+# as float64); a mode writes at most one large float32 array plus small ones,
+# so a dump stays well under 64 MB.
+DUMP_MAX_ELEMS = 6 * 1024 * 1024
+DUMP_SEED = 2468
+
+
+def dump_outputs(dirname, outputs):
+    """Write ``{name: tensor}`` as ``dirname/<name>.npy``. Floating tensors
+    are stored as float32, integer ones as float64. A tensor above the cap is
+    reduced to a seeded, sorted sample of its leading-dimension rows -- the
+    same rows on every run with the same arguments."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        row_elems = max(t[0].numel(), 1) if t.shape[0] else 1
+        keep = max(DUMP_MAX_ELEMS // row_elems, 1)
+        if t.shape[0] > keep:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            sel = torch.randperm(t.shape[0], generator=g)[:keep].sort().values
+            t = t[sel.to(t.device)]
+        t = t.cpu()
+        t = t.to(torch.float32 if t.is_floating_point() else torch.float64)
+        np.save(os.path.join(dirname, name + ".npy"), t.numpy())
 
 
 def run_selfchecks(args, store, rank, world, use_cuda, device):
@@ -176,6 +223,10 @@ def main():
 
     from ddstore_amd import DDStore, PrefetchLoader
 
+    # same arguments -> same shard contents and model weights on every run,
+    # so --dump-outputs of two builds can be compared output for output
+    torch.manual_seed(1234 + rank)
+
     store = DDStore(device=device if use_cuda else "cpu")
     rows, dim, batch = args.rows, args.dim, args.batch
     tdev = device if use_cuda else "cpu"
@@ -223,6 +274,7 @@ def main():
         got += share.numel()
     order = torch.cat(order)[:need]
 
+    last = {}  # what the most recent step handed back to its caller
     store.epoch_begin()
     if args.mode == "train":
         # overlap config: side-stream prefetch feeding a full bf16 train step
@@ -242,7 +294,8 @@ def main():
 
         def run_steps(n: int):
             for _ in range(n):
-                trainer(next_batch())
+                b = next_batch()
+                last["batch"], last["loss"] = b, trainer(b)
 
     elif args.mode == "fetch":
         # flagship store metric: back-to-back batched gathers (owner lookup +
@@ -278,6 +331,8 @@ def main():
                 fetch_one("bench", step_idx[k % nslots], bufs[k % nring])
                 k += 1
             counter["k"] = k
+            if n:
+                last["batch"] = bufs[(k - 1) % nring]
 
     if args.mode == "csr":
         # variable-length fetch: capacity ring buffers sized for the worst
@@ -300,17 +355,20 @@ def main():
 
         def run_steps(n: int):
             k = counter["k"]
+            ret = None
             if streams is None:
                 for _ in range(n):
-                    store.get_csr("bench", step_idx[k % nslots], out=bufs[k % nring])
+                    ret = store.get_csr("bench", step_idx[k % nslots], out=bufs[k % nring])
                     k += 1
             else:
                 for _ in range(n):
                     with torch.cuda.stream(streams[k % 2]):
-                        store.get_csr("bench", step_idx[k % nslots],
-                                      out=bufs[k % nring])
+                        ret = store.get_csr("bench", step_idx[k % nslots],
+                                            out=bufs[k % nring])
                     k += 1
             counter["k"] = k
+            if ret is not None:
+                last["values"], last["offsets"] = ret
 
     run_steps(args.warmup)
 
@@ -345,46 +403,60 @@ def main():
     row_bytes = dim * (stored_itemsize if args.mode != "csr" else 4)
     sps = n_samples / elapsed
 
-    # MEASURED per-owner traffic of the exact timed indices (VERDICT r1:
-    # report counters, not the (N-1)/N estimate). In fetch/csr mode the timed
-    # loop visits slot (warmup+i) % nslots; in train mode the loader consumed
-    # batches [warmup, warmup+steps) of `order` sequentially.
-    import numpy as np
+    extra = {}
+    if args.mode != "csr":
+        extra["gather_GBps_aggregate"] = n_samples * row_bytes / elapsed / 1e9
+    if args.full:
+        # MEASURED per-owner traffic of the exact timed indices (VERDICT r1:
+        # report counters, not the (N-1)/N estimate). In fetch/csr mode the
+        # timed loop visits slot (warmup+i) % nslots; in train mode the loader
+        # consumed batches [warmup, warmup+steps) of `order` sequentially.
+        import numpy as np
 
-    prefix_np = np.asarray(store.query("bench")["prefix"], dtype=np.int64)
-    goff_np = (
-        store._meta("bench")["goff"].numpy() if args.mode == "csr" else None
-    )
-    unit_bytes = 4 if args.mode == "csr" else row_bytes  # per elem vs per row
-    if args.mode == "train":
-        timed_np = order[args.warmup * batch : (args.warmup + args.steps) * batch].numpy()
-        local_b, remote_b = measured_remote_bytes(
-            timed_np, prefix_np, rank, unit_bytes, goff_np
+        prefix_np = np.asarray(store.query("bench")["prefix"], dtype=np.int64)
+        goff_np = (
+            store._meta("bench")["goff"].numpy() if args.mode == "csr" else None
         )
-    else:
-        order_np = order.numpy()
-        per_slot = [
-            measured_remote_bytes(
-                order_np[k * batch : (k + 1) * batch], prefix_np, rank,
-                unit_bytes, goff_np,
+        unit_bytes = 4 if args.mode == "csr" else row_bytes  # per elem vs per row
+        if args.mode == "train":
+            timed_np = order[args.warmup * batch : (args.warmup + args.steps) * batch].numpy()
+            local_b, remote_b = measured_remote_bytes(
+                timed_np, prefix_np, rank, unit_bytes, goff_np
             )
-            for k in range(nslots)
-        ]
-        local_b = remote_b = 0
-        for i in range(args.steps):
-            l, r = per_slot[(args.warmup + i) % nslots]
-            local_b += l
-            remote_b += r
-    if world > 1:
-        red_dev = device if (use_cuda and dist.get_backend() == "nccl") else "cpu"
-        tb = torch.tensor([local_b, remote_b], device=red_dev, dtype=torch.float64)
-        dist.all_reduce(tb, op=dist.ReduceOp.SUM)
-        local_b, remote_b = float(tb[0].item()), float(tb[1].item())
+        else:
+            order_np = order.numpy()
+            per_slot = [
+                measured_remote_bytes(
+                    order_np[k * batch : (k + 1) * batch], prefix_np, rank,
+                    unit_bytes, goff_np,
+                )
+                for k in range(nslots)
+            ]
+            local_b = remote_b = 0
+            for i in range(args.steps):
+                l, r = per_slot[(args.warmup + i) % nslots]
+                local_b += l
+                remote_b += r
+        if world > 1:
+            red_dev = device if (use_cuda and dist.get_backend() == "nccl") else "cpu"
+            tb = torch.tensor([local_b, remote_b], device=red_dev, dtype=torch.float64)
+            dist.all_reduce(tb, op=dist.ReduceOp.SUM)
+            local_b, remote_b = float(tb[0].item()), float(tb[1].item())
+        if args.mode == "csr":
+            # true var-length bytes
+            extra["gather_GBps_aggregate"] = (local_b + remote_b) / elapsed / 1e9
+        # measured from the exact timed indices + directory (owner
+        # histogram), aggregated over ranks -- NOT an (N-1)/N estimate
+        extra["remote_read_GBps_aggregate"] = remote_b / elapsed / 1e9
+        extra["remote_bytes_measured"] = remote_b
+        extra["local_bytes_measured"] = local_b
+        extra["store_stats_rank0"] = store.stats().get("bench", {})
 
-    gather_gbps = n_samples * row_bytes / elapsed / 1e9
-    if args.mode == "csr":
-        gather_gbps = (local_b + remote_b) / elapsed / 1e9  # true var-length bytes
-    remote_gbps = remote_b / elapsed / 1e9
+    if args.dump_outputs and rank == 0:
+        if "values" in last:
+            # only the packed prefix of the capacity buffer is output
+            last["values"] = last["values"][: int(last["offsets"][-1].item())]
+        dump_outputs(args.dump_outputs, last)
 
     if rank == 0:
         result = {
@@ -414,15 +486,7 @@ def main():
                 "parallelism": f"dp{world}",
                 "mode": args.mode,
             },
-            "extra": {
-                "gather_GBps_aggregate": gather_gbps,
-                # measured from the exact timed indices + directory (owner
-                # histogram), aggregated over ranks -- NOT an (N-1)/N estimate
-                "remote_read_GBps_aggregate": remote_gbps,
-                "remote_bytes_measured": remote_b,
-                "local_bytes_measured": local_b,
-                "store_stats_rank0": store.stats().get("bench", {}),
-            },
+            "extra": extra,
         }
         print(json.dumps(result))
 

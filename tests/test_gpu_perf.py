@@ -3,10 +3,13 @@ within ~20% of their tuned round-1 numbers (profiles/microbench.txt).
 Thresholds are deliberately loose to absorb DVFS/box variance (~5%) while
 catching real regressions (the kind that halved bandwidth during tuning)."""
 import json
+import os
 import subprocess
 import sys
 
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
@@ -24,7 +27,7 @@ CSR_FLOOR = 3500  # measured 4359
 def test_gather_bandwidth_floors():
     out = subprocess.run(
         [sys.executable, "tools/microbench.py", "--json"],
-        capture_output=True, text=True, timeout=500,
+        cwd=ROOT, capture_output=True, text=True, timeout=500,
     )
     assert out.returncode == 0, out.stderr[-1500:]
     res = json.loads(out.stdout.strip().splitlines()[-1])
@@ -132,7 +135,7 @@ def test_bench_mode_floors():
         out = subprocess.run(
             [sys.executable, "bench.py", "--steps", "300", "--warmup", "50",
              "--mode", mode],
-            capture_output=True, text=True, timeout=300,
+            cwd=ROOT, capture_output=True, text=True, timeout=300,
         )
         assert out.returncode == 0, out.stderr[-1500:]
         val = json.loads(out.stdout.strip().splitlines()[-1])["value"]
