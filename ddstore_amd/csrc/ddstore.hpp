@@ -593,6 +593,7 @@ public:
         // must NOT silently reinterpret bits (the CPU path converts too)
         int out_t = dds_type_of(out);
         ddstore::gather_rows(stream(), (const void* const*)v.d_peers, v.d_prefix,
+                             (const void* const*)v.peers.data(), v.prefix.data(),
                              nparts_, idx.data_ptr<int64_t>(), nidx, v.row_elems,
                              v.dds_t, out_t, out.data_ptr(), v.d_oob);
         v.n_gather += 1;
@@ -616,7 +617,8 @@ public:
         TORCH_CHECK(out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
                     "ddstore gather: affine output must be f32/f16/bf16");
         ddstore::gather_rows_affine(stream(), (const void* const*)v.d_peers,
-                                    v.d_prefix, nparts_, idx.data_ptr<int64_t>(),
+                                    v.d_prefix, (const void* const*)v.peers.data(),
+                                    v.prefix.data(), nparts_, idx.data_ptr<int64_t>(),
                                     nidx, v.row_elems, v.dds_t, out_t,
                                     (float)scale, (float)shift, out.data_ptr(),
                                     v.d_oob);

@@ -40,7 +40,20 @@ enum DDSType : int {
 #define DDS_CTR_ELEMS 2
 #define DDS_NCTR 3
 
+// Worlds up to this size (one node, the design point) get the owner
+// directory BY VALUE in the gather kernel's arguments; larger ones stage the
+// device copy in LDS.
+#define DDS_DIR_KPARTS 8
+
 namespace ddstore {
+
+// Kernel-argument form of the directory. The host pads prefix[k] for
+// k >= nparts with the total row count (so prefix[DDS_DIR_KPARTS] is always
+// the total and owner lookup needs no nparts) and base[k] with nullptr.
+struct GatherDirK {
+    int64_t prefix[DDS_DIR_KPARTS + 1];
+    const void* base[DDS_DIR_KPARTS];
+};
 
 // Gather `nidx` fixed-stride rows (row = `row_elems` elements of dtype
 // `in_t`) addressed by global row ids `d_idx` from the sharded store
@@ -48,20 +61,30 @@ namespace ddstore {
 // contiguously into `d_out` with dtype `out_t`.
 //   d_peer_base : device array[nparts]   -- shard base pointers (self + IPC peers)
 //   d_prefix    : device array[nparts+1] -- global row prefix sums, prefix[0]=0
+//   h_peer_base : HOST copy of d_peer_base (array[nparts])
+//   h_prefix    : HOST copy of d_prefix (array[nparts+1])
+// The host copies feed the kernel-argument directory of the tiled kernel
+// (nparts <= DDS_DIR_KPARTS); the device copies serve the LDS-staged
+// variant and the scalar fallbacks. Both must describe the same shards.
 // d_oob: device counter incremented once per out-of-range index (the row is
 // skipped instead of read out of bounds; checked lazily via query()).
 void gather_rows(hipStream_t stream,
                  const void* const* d_peer_base,
-                 const int64_t* d_prefix, int nparts,
+                 const int64_t* d_prefix,
+                 const void* const* h_peer_base,
+                 const int64_t* h_prefix, int nparts,
                  const int64_t* d_idx, int64_t nidx,
                  int64_t row_elems, int in_t, int out_t,
                  void* d_out, unsigned long long* d_oob);
 
 // Fused affine gather: out = cast(in) * scale + shift (f32 math; float
 // output dtypes only) -- data-loader normalization folded into the fetch.
+// Directory arguments as for gather_rows.
 void gather_rows_affine(hipStream_t stream,
                         const void* const* d_peer_base,
-                        const int64_t* d_prefix, int nparts,
+                        const int64_t* d_prefix,
+                        const void* const* h_peer_base,
+                        const int64_t* h_prefix, int nparts,
                         const int64_t* d_idx, int64_t nidx,
                         int64_t row_elems, int in_t, int out_t,
                         float scale, float shift,

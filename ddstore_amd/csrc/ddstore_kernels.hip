@@ -11,8 +11,11 @@
 //    per instruction, the gfx950 coalescing sweet spot.
 //  - The owner directory (world_size+1 prefix sums, <=8 on one node) is
 //    staged in LDS; owner lookup is a ~3-7 step binary search over LDS.
+//    The tiled fixed-stride gather takes it in its kernel arguments instead
+//    when it fits (see k_gather_tiled).
 //  - Grids are grid-stride with a cap: >>256 workgroups to fill 8 XCDs,
-//    capped so small launches don't pay dispatch for idle blocks.
+//    capped so small launches don't pay dispatch for idle blocks. The tiled
+//    gather runs a persistent grid sized from the CU count.
 
 #include "ddstore_kernels.h"
 
@@ -21,6 +24,7 @@
 #include <hip/hip_fp8.h>
 #include <type_traits>
 #include <cstdlib>
+#include <string>
 
 namespace ddstore {
 
@@ -211,6 +215,232 @@ k_gather_rows_affine(const void* const* peer_base, const int64_t* gprefix, int n
         for (int k = 0; k < VEC; ++k)
             vout.v[k] = cvt<Tout>(fmaf(to_f32(vin.v[k]), scale, shift));
         *reinterpret_cast<Vout*>(out + t * VEC) = vout;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Tiled gather core (identity / cast / affine share it).
+//
+// A persistent grid of waves loops over TILES of consecutive output rows.
+// Per tile, lane L of the wave loads idx[row0 + L] (one coalesced load for up
+// to 64 rows), resolves the owner and forms the row's source address ONCE
+// (the only 64-bit arithmetic), and the wave then sweeps the tile's chunks
+// in passes of 64 lanes: chunk j = pass * 64 + lane belongs to tile row
+// j / cpr, whose source address comes from that row's lane by a wave
+// shuffle. (row, chunk-in-row) advance incrementally per pass, so the loop
+// has no division and all per-chunk arithmetic is 32-bit. U passes are
+// issued back to back before the first convert/store: U * INB bytes per lane
+// in flight (f32->bf16: 4 passes = 8 dwordx4 loads, 16 rows per wave). The
+// next tile's indices are fetched before the current payload is waited on.
+// The store side stays exactly 16 B per lane, contiguous across the wave.
+//
+// Directory: for nparts <= DDS_DIR_KPARTS it arrives BY VALUE in the kernel
+// arguments (scalar registers: no global loads, no LDS staging, no barrier);
+// the host pads prefix[k >= nparts] with the total, so the unrolled compare
+// chain `prefix[k] <= g` picks the largest k < nparts with prefix[k] <= g,
+// exactly what owner_of's binary search returns (empty parts included).
+// LDSDIR = true keeps the LDS-staged directory for larger worlds, paid once
+// per persistent block.
+//
+// Measured (MI355X, flagship 262,144 x 512-B f32 rows -> bf16; 2048 blocks,
+// 16-row tiles = one group of 4 passes, 2 tiles per wave, nontemporal
+// stores): kernel 43.9 -> 38.5 us, 4.63 -> 5.28 TB/s r+w
+// (profiles/gather_tiled_ab.txt).
+// ---------------------------------------------------------------------------
+struct XfIdentity {
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v) const { return v; }
+};
+struct XfCast {
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v) const { return cvt<Tout>(v); }
+};
+struct XfAffine {
+    float scale, shift;
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v) const {
+        return cvt<Tout>(fmaf(to_f32(v), scale, shift));
+    }
+};
+
+typedef uint32_t dds_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t dds_u32x2 __attribute__((ext_vector_type(2)));
+#define DDS_GLOBAL_AS __attribute__((address_space(1)))
+
+// The packed output is written once and not read back by the gather, so it
+// is stored NON-TEMPORAL: measured on MI355X at the flagship shape (262,144
+// x 512-B f32 rows -> bf16, 4 rotating 64-MiB outputs) plain stores 42.96 us,
+// nontemporal stores 38.50 us per step; nontemporal LOADS of the payload
+// 40.20 us alone and 39.40 us together with the stores, so loads stay plain
+// (profiles/gather_tiled_ab.txt).
+template <typename V>
+__device__ __forceinline__ void store_out(V* p, const V& v) {
+    static_assert(sizeof(V) == 16, "store side is exactly 16 B per lane");
+    dds_u32x4 w;
+    __builtin_memcpy(&w, &v, 16);
+    __builtin_nontemporal_store(w, reinterpret_cast<dds_u32x4*>(p));
+}
+
+// Load sizeof(V) bytes through an explicit GLOBAL pointer: the address went
+// through a wave shuffle as an integer, so the compiler would otherwise emit
+// flat_load (which also occupies lgkmcnt).
+template <typename V>
+__device__ __forceinline__ V load_global(uintptr_t a) {
+    constexpr int B = sizeof(V);
+    V r;
+    if constexpr (B % 16 == 0) {
+        dds_u32x4 w[B / 16];
+#pragma unroll
+        for (int i = 0; i < B / 16; ++i)
+            w[i] = ((const DDS_GLOBAL_AS dds_u32x4*)a)[i];
+        __builtin_memcpy(&r, w, B);
+    } else if constexpr (B == 8) {
+        const dds_u32x2 w = *(const DDS_GLOBAL_AS dds_u32x2*)a;
+        __builtin_memcpy(&r, &w, B);
+    } else if constexpr (B == 4) {
+        const uint32_t w = *(const DDS_GLOBAL_AS uint32_t*)a;
+        __builtin_memcpy(&r, &w, B);
+    } else {
+        static_assert(B == 2, "unsupported vector size");
+        const uint16_t w = *(const DDS_GLOBAL_AS uint16_t*)a;
+        __builtin_memcpy(&r, &w, B);
+    }
+    return r;
+}
+
+// passes issued back to back: ~128 B per lane in flight, 1..8 passes
+template <int INB>
+constexpr int tiled_unroll() {
+    return INB >= 128 ? 1 : (128 / INB > 8 ? 8 : 128 / INB);
+}
+
+template <typename Tin, typename Tout, typename Xf, bool LDSDIR>
+__global__ void __launch_bounds__(kBlock)
+k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
+               const int64_t* gprefix, int nparts,
+               const int64_t* __restrict__ idx, int64_t nidx, int64_t ntiles,
+               uint32_t cpr, uint32_t tile_rows, Xf xf,
+               Tout* __restrict__ out, unsigned long long* oob) {
+    constexpr int VEC = 16 / sizeof(Tout);
+    constexpr int INB = VEC * sizeof(Tin);
+    constexpr int U = tiled_unroll<INB>();
+    using Vin = VecT<Tin, VEC>;
+    using Vout = VecT<Tout, VEC>;
+    __shared__ int64_t s_prefix[LDSDIR ? DDS_MAX_PARTS + 1 : 1];
+    __shared__ uintptr_t s_base[LDSDIR ? DDS_MAX_PARTS : 1];
+    if constexpr (LDSDIR) {
+        for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
+        for (int i = threadIdx.x; i < nparts; i += kBlock)
+            s_base[i] = reinterpret_cast<uintptr_t>(peer_base[i]);
+        __syncthreads();
+    }
+    const int64_t total = LDSDIR ? s_prefix[nparts] : dir.prefix[DDS_DIR_KPARTS];
+
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wstride = (int64_t)gridDim.x * (kBlock / 64);
+    int64_t tile = (int64_t)blockIdx.x * (kBlock / 64) + wave;
+    if (tile >= ntiles) return;
+
+    // chunk j of a tile -> (row-in-tile, chunk-in-row); a tile starts on a
+    // row boundary, so the walk starts from (lane / cpr, lane % cpr) in every
+    // tile and advances by 64 chunks per pass
+    const uint32_t q64 = 64u / cpr, r64 = 64u % cpr;
+    const uint32_t rl0 = lane / cpr, c0 = lane - rl0 * cpr;
+    const int64_t row_bytes = (int64_t)cpr * INB;
+
+    int64_t g_next = 0;
+    {
+        const int64_t r = tile * tile_rows + lane;
+        if (lane < tile_rows && r < nidx) g_next = idx[r];
+    }
+    for (; tile < ntiles; tile += wstride) {
+        const int64_t row0 = tile * tile_rows;
+        const int64_t left = nidx - row0;
+        const uint32_t nrows = left < (int64_t)tile_rows ? (uint32_t)left : tile_rows;
+        const int64_t g = g_next;
+        if (tile + wstride < ntiles) {  // next tile's indices, ahead of the payload
+            const int64_t r = (tile + wstride) * tile_rows + lane;
+            if (lane < tile_rows && r < nidx) g_next = idx[r];
+        }
+        // per-row work, once: bounds, owner, source address (0 = skip)
+        uintptr_t src = 0;
+        if (lane < nrows) {
+            if (g < 0 || g >= total) {
+                atomicAdd(oob, 1ull);
+            } else if constexpr (LDSDIR) {
+                const int p = owner_of(s_prefix, nparts, g);
+                src = s_base[p] + (uintptr_t)((g - s_prefix[p]) * row_bytes);
+            } else {
+                int64_t pf = dir.prefix[0];
+                uintptr_t bs = reinterpret_cast<uintptr_t>(dir.base[0]);
+#pragma unroll
+                for (int k = 1; k < DDS_DIR_KPARTS; ++k) {
+                    const bool ge = dir.prefix[k] <= g;
+                    pf = ge ? dir.prefix[k] : pf;
+                    bs = ge ? reinterpret_cast<uintptr_t>(dir.base[k]) : bs;
+                }
+                src = bs + (uintptr_t)((g - pf) * row_bytes);
+            }
+        }
+        Vout* __restrict__ op = reinterpret_cast<Vout*>(out) + row0 * cpr;
+        const uint32_t nch = nrows * cpr;
+        // a tile without skipped rows runs its full groups branch-free: the
+        // U passes' loads are then issued back to back and waited on with
+        // counted vmcnt (loads behind per-lane branches make the compiler
+        // wait for ALL outstanding loads before each next one)
+        const bool clean = __ballot(lane < nrows && src == 0) == 0;
+        uint32_t rl = rl0, c = c0;
+        for (uint32_t jb = 0; jb < nch; jb += 64u * U) {  // wave-uniform
+            if (clean && jb + 64u * U <= nch) {
+                Vin vin[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const uintptr_t sp =
+                        (uintptr_t)__shfl((unsigned long long)src, (int)(rl & 63u));
+                    vin[u] = load_global<Vin>(sp + (uintptr_t)(c * (uint32_t)INB));
+                    c += r64;
+                    rl += q64;
+                    if (c >= cpr) {
+                        c -= cpr;
+                        rl += 1;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    Vout vout;
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k)
+                        vout.v[k] = xf.template apply<Tout>(vin[u].v[k]);
+                    store_out(&op[jb + 64u * u + lane], vout);
+                }
+            } else {
+                // partial group or a tile with skipped rows: one pass at a
+                // time, load and store under the same per-lane predicate
+#pragma unroll 1
+                for (int u = 0; u < U; ++u) {
+                    const uint32_t j = jb + 64u * u + lane;
+                    // every lane takes part in the shuffle
+                    const uintptr_t sp =
+                        (uintptr_t)__shfl((unsigned long long)src, (int)(rl & 63u));
+                    if (j < nch && sp != 0) {
+                        const Vin v =
+                            load_global<Vin>(sp + (uintptr_t)(c * (uint32_t)INB));
+                        Vout vout;
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k)
+                            vout.v[k] = xf.template apply<Tout>(v.v[k]);
+                        store_out(&op[j], vout);
+                    }
+                    c += r64;
+                    rl += q64;
+                    if (c >= cpr) {
+                        c -= cpr;
+                        rl += 1;
+                    }
+                }
+            }
+        }
     }
 }
 
@@ -780,12 +1010,141 @@ inline int dds_itemsize(int t) {
     }
 }
 
+// Both copies of one variable's directory (see ddstore_kernels.h).
+struct DirArgs {
+    const void* const* d_pb;
+    const int64_t* d_pf;
+    const void* const* h_pb;
+    const int64_t* h_pf;
+    int np;
+};
+
+// A/B knobs of the fixed-stride gather, read once (docs/API.md):
+//   DDSTORE_GATHER_KERNEL=legacy|tiled  force one kernel family (default:
+//                                       by row size, see kTiledMinCpr)
+//   DDSTORE_GATHER_BLOCKS=<n>           size of the persistent grid (still
+//                                       never more than the work)
+//   DDSTORE_GATHER_DIR=lds              LDS directory even at small nparts
+//   DDSTORE_GATHER_TILE_ROWS=<n>        cap rows per tile (1..64)
+struct GatherKnobs {
+    int kernel = 0;  // 0 auto, 1 legacy, 2 tiled
+    int blocks = 0;
+    bool dir_lds = false;
+    int tile_rows = 64;
+};
+const GatherKnobs& gather_knobs() {
+    static const GatherKnobs k = [] {
+        GatherKnobs g;
+        if (const char* e = getenv("DDSTORE_GATHER_KERNEL")) {
+            const std::string s(e);
+            g.kernel = s == "legacy" ? 1 : (s == "tiled" ? 2 : 0);
+        }
+        if (const char* e = getenv("DDSTORE_GATHER_BLOCKS")) {
+            const int v = atoi(e);
+            if (v > 0) g.blocks = v;
+        }
+        if (const char* e = getenv("DDSTORE_GATHER_DIR"))
+            g.dir_lds = std::string(e) == "lds";
+        if (const char* e = getenv("DDSTORE_GATHER_TILE_ROWS")) {
+            const int v = atoi(e);
+            if (v >= 1 && v <= 64) g.tile_rows = v;
+        }
+        return g;
+    }();
+    return k;
+}
+
+// CU count of the device the store runs on (one device per process),
+// queried once.
+int cu_count() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
+                hipSuccess || v <= 0)
+            v = 256;
+        return v;
+    }();
+    return n;
+}
+
+// Persistent grid: kBlocksPerCU workgroups of 4 waves per CU (8 = every wave
+// slot at occupancy 8), never more than the work. Flagship step time by
+// grid on MI355X (256 CUs): 512 blocks 38.99 us, 1024 37.98, 2048 37.65 to
+// 38.48 (two run modes), 4096 37.42 -- flat once the wave slots are full.
+constexpr int kBlocksPerCU = 8;
+// Tiles are sized so that every wave gets about this many when the batch
+// allows: fewer leaves wave slots idle, more only shrinks the tile.
+constexpr int kTilesPerWave = 2;
+// Rows with more chunks than this go to the legacy one-shot mapping: a tile
+// is at least one row, and one wave per multi-hundred-KiB row starves the
+// chip at small batches.
+constexpr int64_t kTiledMaxCpr = 4096;
+// Rows with fewer 16-B output chunks than this keep the legacy mapping: a
+// tile of <=64 such rows is only a pass or two, so nothing is in flight to
+// pay for the tile setup. Measured on MI355X, B=131072, legacy / tiled:
+//   f32->f32   64-B rows (4 chunks)   6.05 / 6.44 us
+//   u8->f32    16-B rows (4 chunks)   5.81 / 6.43 us
+//   f32->bf16 128-B rows (4 chunks)   6.15 / 5.90 us
+//   f32->f32  128-B rows (8 chunks)   8.61 / 7.13 us
+//   f32->bf16 256-B rows (8 chunks)  11.79 / 10.12 us
+constexpr int64_t kTiledMinCpr = 8;
+
+// Launch the tiled core if the shape is eligible; false = caller falls back.
+// `re` = elements per row, counted in Tin/Tout elements.
+template <typename Tin, typename Tout, typename Xf>
+bool launch_tiled(hipStream_t stream, const DirArgs& d, const int64_t* idx,
+                  int64_t n, int64_t re, Xf xf, Tout* out,
+                  unsigned long long* oob) {
+    constexpr int VEC = 16 / sizeof(Tout);
+    constexpr int INB = VEC * (int)sizeof(Tin);
+    constexpr int U = tiled_unroll<INB>();
+    const GatherKnobs& kn = gather_knobs();
+    if (kn.kernel == 1 || re % VEC != 0 || ((uintptr_t)out % 16) != 0) return false;
+    const int64_t cpr = re / VEC;
+    if (cpr > kTiledMaxCpr) return false;
+    if (kn.kernel != 2 && cpr < kTiledMinCpr) return false;
+
+    int64_t blocks_max = (int64_t)cu_count() * kBlocksPerCU;
+    if (kn.blocks > 0) blocks_max = kn.blocks;
+    // rows covered by one group of U passes: the smallest useful tile
+    int64_t tr_min = (64 * U + cpr - 1) / cpr;
+    int64_t tr = n / (blocks_max * (kBlock / 64) * kTilesPerWave);
+    if (tr < tr_min) tr = tr_min;
+    if (tr > kn.tile_rows) tr = kn.tile_rows;
+    const int64_t ntiles = (n + tr - 1) / tr;
+    int64_t grid = (ntiles + (kBlock / 64) - 1) / (kBlock / 64);
+    if (grid > blocks_max) grid = blocks_max;
+
+    if (d.np <= DDS_DIR_KPARTS && !kn.dir_lds) {
+        GatherDirK dir;
+        const int64_t total = d.h_pf[d.np];
+        for (int k = 0; k <= DDS_DIR_KPARTS; ++k)
+            dir.prefix[k] = k < d.np ? d.h_pf[k] : total;
+        for (int k = 0; k < DDS_DIR_KPARTS; ++k)
+            dir.base[k] = k < d.np ? d.h_pb[k] : nullptr;
+        hipLaunchKernelGGL((k_gather_tiled<Tin, Tout, Xf, false>), dim3((unsigned)grid),
+                           dim3(kBlock), 0, stream, dir, d.d_pb, d.d_pf, d.np, idx, n,
+                           ntiles, (uint32_t)cpr, (uint32_t)tr, xf, out, oob);
+    } else {
+        GatherDirK dir = {};
+        hipLaunchKernelGGL((k_gather_tiled<Tin, Tout, Xf, true>), dim3((unsigned)grid),
+                           dim3(kBlock), 0, stream, dir, d.d_pb, d.d_pf, d.np, idx, n,
+                           ntiles, (uint32_t)cpr, (uint32_t)tr, xf, out, oob);
+    }
+    return true;
+}
+
 template <typename Tin, typename Tout>
-void launch_gather_cast_one(hipStream_t stream, const void* const* pb,
-                            const int64_t* pf, int np, const int64_t* idx,
+void launch_gather_cast_one(hipStream_t stream, const DirArgs& d,
+                            const int64_t* idx,
                             int64_t n, int64_t re, Tout* out,
                             unsigned long long* oob) {
     constexpr int VEC = 16 / sizeof(Tout);
+    if (launch_tiled<Tin, Tout>(stream, d, idx, n, re, XfCast{}, out, oob)) return;
+    const void* const* pb = d.d_pb;
+    const int64_t* pf = d.d_pf;
+    const int np = d.np;
     if (re % VEC == 0 && ((uintptr_t)out % 16) == 0) {
         const int grid = n_blocks(n * (re / VEC));
         hipLaunchKernelGGL((k_gather_rows_castv<Tin, Tout>), dim3(grid), dim3(kBlock),
@@ -798,14 +1157,14 @@ void launch_gather_cast_one(hipStream_t stream, const void* const* pb,
 }
 
 template <typename Tin>
-void launch_gather_cast_out(hipStream_t stream, const void* const* pb,
-                            const int64_t* pf, int np, const int64_t* idx,
+void launch_gather_cast_out(hipStream_t stream, const DirArgs& d,
+                            const int64_t* idx,
                             int64_t n, int64_t re, int out_t, void* out,
                             unsigned long long* oob) {
     switch (out_t) {
 #define DDS_OUT(tag, T)                                                               \
     case tag:                                                                         \
-        launch_gather_cast_one<Tin, T>(stream, pb, pf, np, idx, n, re, (T*)out, oob); \
+        launch_gather_cast_one<Tin, T>(stream, d, idx, n, re, (T*)out, oob);          \
         break;
         DDS_OUT(DDS_U8, uint8_t)
         DDS_OUT(DDS_I32, int32_t)
@@ -823,14 +1182,19 @@ void launch_gather_cast_out(hipStream_t stream, const void* const* pb,
 } // namespace
 
 template <typename Tin>
-void launch_affine_out(hipStream_t stream, const void* const* pb, const int64_t* pf,
-                       int np, const int64_t* idx, int64_t n, int64_t re,
+void launch_affine_out(hipStream_t stream, const DirArgs& d,
+                       const int64_t* idx, int64_t n, int64_t re,
                        float a, float b, int out_t, void* out,
                        unsigned long long* oob) {
+    const void* const* pb = d.d_pb;
+    const int64_t* pf = d.d_pf;
+    const int np = d.np;
 #define DDS_AFF(tag, T)                                                              \
     case tag: {                                                                      \
         constexpr int VEC = 16 / sizeof(T);                                          \
-        if (re % VEC == 0 && ((uintptr_t)out % 16) == 0) {                           \
+        if (launch_tiled<Tin, T>(stream, d, idx, n, re, XfAffine{a, b}, (T*)out,     \
+                                 oob)) {                                             \
+        } else if (re % VEC == 0 && ((uintptr_t)out % 16) == 0) {                    \
             const int grid = n_blocks(n * (re / VEC));                               \
             hipLaunchKernelGGL((k_gather_rows_affine<Tin, T>), dim3(grid),           \
                                dim3(kBlock), 0, stream, pb, pf, np, idx, n, re, a,   \
@@ -853,16 +1217,19 @@ void launch_affine_out(hipStream_t stream, const void* const* pb, const int64_t*
 
 void gather_rows_affine(hipStream_t stream,
                         const void* const* d_peer_base,
-                        const int64_t* d_prefix, int nparts,
+                        const int64_t* d_prefix,
+                        const void* const* h_peer_base,
+                        const int64_t* h_prefix, int nparts,
                         const int64_t* d_idx, int64_t nidx,
                         int64_t row_elems, int in_t, int out_t,
                         float scale, float shift,
                         void* d_out, unsigned long long* d_oob) {
     if (nidx == 0 || row_elems == 0) return;
+    const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
     switch (in_t) {
 #define DDS_AIN(tag, T)                                                          \
     case tag:                                                                    \
-        launch_affine_out<T>(stream, d_peer_base, d_prefix, nparts, d_idx,       \
+        launch_affine_out<T>(stream, dir, d_idx,                                 \
                              nidx, row_elems, scale, shift, out_t, d_out,        \
                              d_oob);                                             \
         break;
@@ -881,11 +1248,14 @@ void gather_rows_affine(hipStream_t stream,
 
 void gather_rows(hipStream_t stream,
                  const void* const* d_peer_base,
-                 const int64_t* d_prefix, int nparts,
+                 const int64_t* d_prefix,
+                 const void* const* h_peer_base,
+                 const int64_t* h_prefix, int nparts,
                  const int64_t* d_idx, int64_t nidx,
                  int64_t row_elems, int in_t, int out_t,
                  void* d_out, unsigned long long* d_oob) {
     if (nidx == 0 || row_elems == 0) return;
+    const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
     const int64_t row_bytes = row_elems * dds_itemsize(in_t);
     // the uint4/VecT paths require a 16/32-B-aligned output pointer; an
     // offset view (e.g. buf[1:]) falls through to the cast/scalar kernels,
@@ -902,6 +1272,15 @@ void gather_rows(hipStream_t stream,
         // A/B on MI355X (B=131072): 512 B rows -- 16B 30.1us / 32B 28.5 /
         // 64B 33.9; 64 B rows -- 16B 6.1 / 32B 6.7 (too few threads per
         // row). 32-B chunks win once a row has >=4 of them.
+        // Both experiments above ran on the one-shot grid (per-block
+        // prologue, one dependent index load per thread). The tiled core
+        // (one index load and owner lookup per ROW, 8 dwordx4 loads in
+        // flight per lane, persistent grid) takes rows of >= 8 chunks:
+        // B=131072, 512 B rows 28.2 -> 23.3 us, 128 B rows 8.6 -> 7.1 us;
+        // 64 B rows stay here (6.05 legacy vs 6.44 tiled).
+        if (launch_tiled<uint32_t, uint32_t>(stream, dir, d_idx, nidx, row_bytes / 4,
+                                             XfIdentity{}, (uint32_t*)d_out, d_oob))
+            return;
         if (row_bytes % 32 == 0 && row_bytes >= 128 && out_align % 32 == 0) {
             const int64_t cpr32 = row_bytes / 32;
             const int grid = n_blocks(nidx * cpr32);
@@ -919,7 +1298,7 @@ void gather_rows(hipStream_t stream,
     switch (in_t) {
 #define DDS_IN(tag, T)                                                           \
     case tag:                                                                    \
-        launch_gather_cast_out<T>(stream, d_peer_base, d_prefix, nparts, d_idx,  \
+        launch_gather_cast_out<T>(stream, dir, d_idx,                            \
                                   nidx, row_elems, out_t, d_out, d_oob);         \
         break;
         DDS_IN(DDS_U8, uint8_t)
