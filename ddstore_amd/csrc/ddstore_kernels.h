@@ -117,7 +117,7 @@ void csr_lens(hipStream_t stream, const int64_t* d_goff, const int64_t* d_idx,
 
 // Balanced one-call CSR fetch: three tiny plan kernels (per-tile lens+scan,
 // single-block tile-aggregate scan, finalize + work-item emission) followed
-// by an item-parallel gather. Samples are split into <=~256-B work items so
+// by an item-parallel gather. Samples are split into <=1024-B work items so
 // gather waves get near-uniform work (the per-sample kernel loses ~1.5x to
 // max-of-N-samples-per-wave imbalance; r2 fixed-len A/B). Writes
 // d_out_off[nidx+1]; accumulates true gathered elements into

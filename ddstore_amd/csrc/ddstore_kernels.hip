@@ -56,6 +56,40 @@ __device__ __forceinline__ int owner_of(const int64_t* prefix, int nparts, int64
     return lo;
 }
 
+// The owner directory staged in LDS, declared `__shared__` by the kernel:
+// the shard base pointers (as P) and NPFX prefix-sum arrays -- prefix[0]
+// counts rows (samples), and the CSR kernels add prefix[1], the element
+// counts. load() is the strided copy from the device arrays plus the barrier.
+template <typename P, int NPFX = 1>
+struct LdsDir {
+    int64_t prefix[NPFX][DDS_MAX_PARTS + 1];
+    P base[DDS_MAX_PARTS];
+
+    __device__ __forceinline__ void load(const void* const* peer_base, int nparts,
+                                         const int64_t* gprefix0,
+                                         const int64_t* gprefix1 = nullptr) {
+        for (int i = threadIdx.x; i <= nparts; i += kBlock) {
+            prefix[0][i] = gprefix0[i];
+            if constexpr (NPFX == 2) prefix[1][i] = gprefix1[i];
+        }
+        for (int i = threadIdx.x; i < nparts; i += kBlock)
+            base[i] = reinterpret_cast<P>(peer_base[i]);
+        __syncthreads();
+    }
+};
+
+template <typename P, int NPFX>
+__device__ __forceinline__ int owner_of(const LdsDir<P, NPFX>& d, int nparts, int64_t row) {
+    return owner_of(d.prefix[0], nparts, row);
+}
+
+// a bad index is skipped and counted by the caller, never read out of bounds
+template <typename P, int NPFX>
+__device__ __forceinline__ bool out_of_range(const LdsDir<P, NPFX>& d, int nparts,
+                                             int64_t g) {
+    return g < 0 || g >= d.prefix[0][nparts];
+}
+
 template <typename T>
 constexpr bool is_fp8_v =
     std::is_same_v<T, __hip_fp8_e4m3> || std::is_same_v<T, __hip_fp8_e5m2>;
@@ -82,138 +116,74 @@ __device__ __forceinline__ Tout cvt(Tin v) {
 }
 
 // ---------------------------------------------------------------------------
-// Fixed-stride row gather, same dtype, row size a multiple of 16 B.
-// Thread t moves 16-B chunk (t % chunks_per_row) of row (t / chunks_per_row):
-// consecutive lanes walk consecutive chunks of one row -> coalesced loads and
-// stores; the per-thread i64 divide is hidden under the memory traffic.
-// ---------------------------------------------------------------------------
-// CHUNK = 16 or 32 bytes per thread. 32 B (two dwordx4 loads in flight per
-// thread) measured faster than 16 B when rows allow -- same finding as the
-// cast kernel, where 32B-read threads beat 16B-read threads on byte rate.
-template <int CHUNK>
-__global__ void __launch_bounds__(kBlock)
-k_gather_rows_b16(const void* const* peer_base, const int64_t* gprefix, int nparts,
-                  const int64_t* idx, int64_t nidx, int64_t chunks_per_row,
-                  uint4* __restrict__ out, unsigned long long* oob) {
-    using V = VecT<uint4, CHUNK / 16>;
-    __shared__ int64_t s_prefix[DDS_MAX_PARTS + 1];
-    __shared__ const V* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const V*>(peer_base[i]);
-    __syncthreads();
-
-    V* __restrict__ vout = reinterpret_cast<V*>(out);
-    const int64_t total = nidx * chunks_per_row;
-    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = t / chunks_per_row;
-        const int64_t c = t - r * chunks_per_row;
-        const int64_t g = idx[r];
-        if (g < 0 || g >= s_prefix[nparts]) {  // skip instead of OOB read
-            if (c == 0) atomicAdd(oob, 1ull);
-            continue;
-        }
-        const int p = owner_of(s_prefix, nparts, g);
-        vout[t] = s_base[p][(g - s_prefix[p]) * chunks_per_row + c];
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Fixed-stride row gather with fused dtype cast, vectorized: each thread
-// moves VEC = 16/max(sizeof(Tin), sizeof(Tout)) elements so the wider side
-// issues full 16-B accesses and the narrower side 16/ratio-B accesses
-// (scalar bf16/f16 loads cost ~2-2.5x -- cdna_hip_programming.md G13).
-// Requires row_elems % VEC == 0 (host falls back to the scalar kernel).
-// ---------------------------------------------------------------------------
-template <typename Tin, typename Tout>
-__global__ void __launch_bounds__(kBlock)
-k_gather_rows_castv(const void* const* peer_base, const int64_t* gprefix, int nparts,
-                    const int64_t* idx, int64_t nidx, int64_t row_elems,
-                    Tout* __restrict__ out, unsigned long long* oob) {
-    // measured optimum on MI355X: the OUTPUT side exactly 16 B per thread,
-    // input side 16*in/out bytes (f32->bf16: 32B-in/16B-out = 21.2 us vs
-    // 27.4 us for 16B/8B; u8->f32: 4B-in/16B-out = 20.9 us vs 26.0 us for
-    // 16B/64B) -- stores are the side that cannot be split by the memory
-    // system, so keep them at dwordx4.
-    constexpr int VEC = 16 / sizeof(Tout);
-    using Vin = VecT<Tin, VEC>;
-    using Vout = VecT<Tout, VEC>;
-    __shared__ int64_t s_prefix[DDS_MAX_PARTS + 1];
-    __shared__ const Tin* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const Tin*>(peer_base[i]);
-    __syncthreads();
-
-    const int64_t cpr = row_elems / VEC;  // vector chunks per row
-    const int64_t total = nidx * cpr;
-    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = t / cpr;
-        const int64_t c = t - r * cpr;
-        const int64_t g = idx[r];
-        if (g < 0 || g >= s_prefix[nparts]) {
-            if (c == 0) atomicAdd(oob, 1ull);
-            continue;
-        }
-        const int p = owner_of(s_prefix, nparts, g);
-        const Vin vin = *reinterpret_cast<const Vin*>(
-            s_base[p] + (g - s_prefix[p]) * row_elems + c * VEC);
-        Vout vout;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) vout.v[k] = cvt<Tout>(vin.v[k]);
-        *reinterpret_cast<Vout*>(out + t * VEC) = vout;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Fused affine gather: out = cast(in) * scale + shift, float outputs only
+// Per-element transforms of the fixed-stride gathers: byte move, dtype cast,
+// and the fused affine out = cast(in) * scale + shift with float outputs only
 // (data-loader normalization fused into the fetch: store u8/fp8/f16 samples,
 // gather normalized f32/bf16/f16 minibatches in one pass). Math in f32.
 // ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ float to_f32(T v) {
-    if constexpr (std::is_same_v<T, __half>) return __half2float(v);
-    else if constexpr (std::is_same_v<T, __hip_bfloat16>) return __bfloat162float(v);
-    else if constexpr (is_fp8_v<T>) return static_cast<float>(v);
-    else return (float)v;
-}
+struct XfIdentity {
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v) const { return v; }
+};
+struct XfCast {
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v) const { return cvt<Tout>(v); }
+};
+struct XfAffine {
+    float scale, shift;
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v) const {
+        return cvt<Tout>(fmaf(cvt<float>(v), scale, shift));
+    }
+};
 
-template <typename Tin, typename Tout>
+// ---------------------------------------------------------------------------
+// One-shot fixed-stride row gather: thread t moves VEC-element chunk
+// (t % chunks_per_row) of row (t / chunks_per_row) through `xf`. Consecutive
+// lanes walk consecutive chunks of one row -> coalesced loads and stores; the
+// per-thread i64 divide is hidden under the memory traffic. Requires
+// row_elems % VEC == 0 and out aligned to VEC elements (the host checks).
+//
+// Cast and affine, VEC = 16 / sizeof(Tout) -- measured optimum on MI355X: the
+// OUTPUT side exactly 16 B per thread, input side 16*in/out bytes (f32->bf16:
+// 32B-in/16B-out = 21.2 us vs 27.4 us for 16B/8B; u8->f32: 4B-in/16B-out =
+// 20.9 us vs 26.0 us for 16B/64B) -- stores are the side that cannot be split
+// by the memory system, so keep them at dwordx4 (scalar bf16/f16 loads cost
+// ~2-2.5x -- cdna_hip_programming.md G13). VEC = 1 is their element-wise
+// fallback for rows or outputs that do not allow it.
+//
+// The same-dtype byte move is XfIdentity with VEC = 1 over a 16-B (uint4) or
+// 32-B (VecT<uint4, 2>) element. 32 B (two dwordx4 loads in flight per
+// thread) measured faster than 16 B when rows allow -- same finding as the
+// cast, where 32B-read threads beat 16B-read threads on byte rate.
+// ---------------------------------------------------------------------------
+template <typename Tin, typename Tout, int VEC, typename Xf>
 __global__ void __launch_bounds__(kBlock)
-k_gather_rows_affine(const void* const* peer_base, const int64_t* gprefix, int nparts,
-                     const int64_t* idx, int64_t nidx, int64_t row_elems,
-                     float scale, float shift,
-                     Tout* __restrict__ out, unsigned long long* oob) {
-    constexpr int VEC = 16 / sizeof(Tout);
+k_gather_oneshot(const void* const* peer_base, const int64_t* gprefix, int nparts,
+                 const int64_t* idx, int64_t nidx, int64_t row_elems, Xf xf,
+                 Tout* __restrict__ out, unsigned long long* oob) {
     using Vin = VecT<Tin, VEC>;
     using Vout = VecT<Tout, VEC>;
-    __shared__ int64_t s_prefix[DDS_MAX_PARTS + 1];
-    __shared__ const Tin* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const Tin*>(peer_base[i]);
-    __syncthreads();
+    __shared__ LdsDir<const Tin*> dir;
+    dir.load(peer_base, nparts, gprefix);
 
-    const int64_t cpr = row_elems / VEC;
+    const int64_t cpr = row_elems / VEC;  // chunks per row
     const int64_t total = nidx * cpr;
     for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * kBlock) {
         const int64_t r = t / cpr;
         const int64_t c = t - r * cpr;
         const int64_t g = idx[r];
-        if (g < 0 || g >= s_prefix[nparts]) {
+        if (out_of_range(dir, nparts, g)) {  // skip instead of OOB read
             if (c == 0) atomicAdd(oob, 1ull);
             continue;
         }
-        const int p = owner_of(s_prefix, nparts, g);
+        const int p = owner_of(dir, nparts, g);
         const Vin vin = *reinterpret_cast<const Vin*>(
-            s_base[p] + (g - s_prefix[p]) * row_elems + c * VEC);
+            dir.base[p] + (g - dir.prefix[0][p]) * row_elems + c * VEC);
         Vout vout;
 #pragma unroll
-        for (int k = 0; k < VEC; ++k)
-            vout.v[k] = cvt<Tout>(fmaf(to_f32(vin.v[k]), scale, shift));
+        for (int k = 0; k < VEC; ++k) vout.v[k] = xf.template apply<Tout>(vin.v[k]);
         *reinterpret_cast<Vout*>(out + t * VEC) = vout;
     }
 }
@@ -247,22 +217,6 @@ k_gather_rows_affine(const void* const* peer_base, const int64_t* gprefix, int n
 // stores): kernel 43.9 -> 38.5 us, 4.63 -> 5.28 TB/s r+w
 // (profiles/gather_tiled_ab.txt).
 // ---------------------------------------------------------------------------
-struct XfIdentity {
-    template <typename Tout, typename Tin>
-    __device__ __forceinline__ Tout apply(Tin v) const { return v; }
-};
-struct XfCast {
-    template <typename Tout, typename Tin>
-    __device__ __forceinline__ Tout apply(Tin v) const { return cvt<Tout>(v); }
-};
-struct XfAffine {
-    float scale, shift;
-    template <typename Tout, typename Tin>
-    __device__ __forceinline__ Tout apply(Tin v) const {
-        return cvt<Tout>(fmaf(to_f32(v), scale, shift));
-    }
-};
-
 typedef uint32_t dds_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t dds_u32x2 __attribute__((ext_vector_type(2)));
 #define DDS_GLOBAL_AS __attribute__((address_space(1)))
@@ -326,15 +280,9 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
     constexpr int U = tiled_unroll<INB>();
     using Vin = VecT<Tin, VEC>;
     using Vout = VecT<Tout, VEC>;
-    __shared__ int64_t s_prefix[LDSDIR ? DDS_MAX_PARTS + 1 : 1];
-    __shared__ uintptr_t s_base[LDSDIR ? DDS_MAX_PARTS : 1];
-    if constexpr (LDSDIR) {
-        for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
-        for (int i = threadIdx.x; i < nparts; i += kBlock)
-            s_base[i] = reinterpret_cast<uintptr_t>(peer_base[i]);
-        __syncthreads();
-    }
-    const int64_t total = LDSDIR ? s_prefix[nparts] : dir.prefix[DDS_DIR_KPARTS];
+    __shared__ LdsDir<uintptr_t> ldir;  // unused, so not allocated, without LDSDIR
+    if constexpr (LDSDIR) ldir.load(peer_base, nparts, gprefix);
+    const int64_t total = LDSDIR ? ldir.prefix[0][nparts] : dir.prefix[DDS_DIR_KPARTS];
 
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -369,8 +317,8 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
             if (g < 0 || g >= total) {
                 atomicAdd(oob, 1ull);
             } else if constexpr (LDSDIR) {
-                const int p = owner_of(s_prefix, nparts, g);
-                src = s_base[p] + (uintptr_t)((g - s_prefix[p]) * row_bytes);
+                const int p = owner_of(ldir, nparts, g);
+                src = ldir.base[p] + (uintptr_t)((g - ldir.prefix[0][p]) * row_bytes);
             } else {
                 int64_t pf = dir.prefix[0];
                 uintptr_t bs = reinterpret_cast<uintptr_t>(dir.base[0]);
@@ -444,119 +392,6 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
     }
 }
 
-// element-wise fallback for row_elems not divisible by VEC
-template <typename Tin, typename Tout>
-__global__ void __launch_bounds__(kBlock)
-k_gather_rows_affine_s(const void* const* peer_base, const int64_t* gprefix, int nparts,
-                       const int64_t* idx, int64_t nidx, int64_t row_elems,
-                       float scale, float shift,
-                       Tout* __restrict__ out, unsigned long long* oob) {
-    __shared__ int64_t s_prefix[DDS_MAX_PARTS + 1];
-    __shared__ const Tin* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const Tin*>(peer_base[i]);
-    __syncthreads();
-    const int64_t total = nidx * row_elems;
-    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = t / row_elems;
-        const int64_t c = t - r * row_elems;
-        const int64_t g = idx[r];
-        if (g < 0 || g >= s_prefix[nparts]) {
-            if (c == 0) atomicAdd(oob, 1ull);
-            continue;
-        }
-        const int p = owner_of(s_prefix, nparts, g);
-        out[t] = cvt<Tout>(fmaf(
-            to_f32(s_base[p][(g - s_prefix[p]) * row_elems + c]), scale, shift));
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Fixed-stride row gather, general: per-element loop with dtype cast.
-// ---------------------------------------------------------------------------
-template <typename Tin, typename Tout>
-__global__ void __launch_bounds__(kBlock)
-k_gather_rows_cast(const void* const* peer_base, const int64_t* gprefix, int nparts,
-                   const int64_t* idx, int64_t nidx, int64_t row_elems,
-                   Tout* __restrict__ out, unsigned long long* oob) {
-    __shared__ int64_t s_prefix[DDS_MAX_PARTS + 1];
-    __shared__ const Tin* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) s_prefix[i] = gprefix[i];
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const Tin*>(peer_base[i]);
-    __syncthreads();
-
-    const int64_t total = nidx * row_elems;
-    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = t / row_elems;
-        const int64_t c = t - r * row_elems;
-        const int64_t g = idx[r];
-        if (g < 0 || g >= s_prefix[nparts]) {
-            if (c == 0) atomicAdd(oob, 1ull);
-            continue;
-        }
-        const int p = owner_of(s_prefix, nparts, g);
-        out[t] = cvt<Tout>(s_base[p][(g - s_prefix[p]) * row_elems + c]);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// CSR gather, chunked: GROUP lanes cooperate per sample (see gather_csr's
-// heuristic note; small groups amortize per-sample setup across the wave).
-// ---------------------------------------------------------------------------
-template <typename T, int GROUP>
-__global__ void __launch_bounds__(kBlock)
-k_gather_csr_wave(const void* const* peer_base,
-                  const int64_t* sample_prefix, const int64_t* elem_prefix, int nparts,
-                  const int64_t* goff,
-                  const int64_t* idx, int64_t nidx,
-                  const int64_t* out_off, int64_t chunks_per_elem,
-                  int64_t cap_elems,
-                  T* __restrict__ out, unsigned long long* ctrs) {
-    __shared__ int64_t s_sprefix[DDS_MAX_PARTS + 1];
-    __shared__ int64_t s_eprefix[DDS_MAX_PARTS + 1];
-    __shared__ const T* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) {
-        s_sprefix[i] = sample_prefix[i];
-        s_eprefix[i] = elem_prefix[i];
-    }
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const T*>(peer_base[i]);
-    __syncthreads();
-
-    constexpr int GPB = kBlock / GROUP;  // sample groups per block
-    const int64_t first = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP;
-    const int64_t step = (int64_t)gridDim.x * GPB;
-    const int tid = threadIdx.x % GROUP;
-    for (int64_t s = first; s < nidx; s += step) {
-        const int64_t g = idx[s];
-        if (g < 0 || g >= s_sprefix[nparts]) {
-            if (tid == 0) atomicAdd(ctrs + DDS_CTR_OOB, 1ull);
-            continue;
-        }
-        const int p = owner_of(s_sprefix, nparts, g);
-        const int64_t e0 = goff[g];
-        const int64_t len = goff[g + 1] - e0;
-        const int64_t o0 = out_off[s];
-        if (o0 < 0 || o0 + len > cap_elems) {  // undersized capacity buffer:
-            if (tid == 0) {                    // never write OOB
-                atomicAdd(ctrs + DDS_CTR_CAP, 1ull);
-                // keep the true-bytes counter honest (see k_csr_plan2)
-                atomicAdd(ctrs + DDS_CTR_ELEMS,
-                          (unsigned long long)(-(long long)len));
-            }
-            continue;
-        }
-        const int64_t nch = len * chunks_per_elem;
-        const T* src = s_base[p] + (e0 - s_eprefix[p]) * chunks_per_elem;
-        T* dst = out + o0 * chunks_per_elem;
-        for (int64_t c = tid; c < nch; c += GROUP) dst[c] = src[c];
-    }
-}
-
 // Per-sample lengths for a CSR gather plan: lens[i] = goff[idx[i]+1] -
 // goff[idx[i]] (one kernel instead of the 3-4 elementwise torch launches
 // the equivalent `goff[idx+1]-goff[idx]` costs per step).
@@ -589,20 +424,12 @@ k_csr_lens(const int64_t* goff, const int64_t* idx, int64_t nidx, int64_t nsampl
 // Copy nd dwords src->dst by `nthreads` cooperating threads (tid strided),
 // with the STORE side aligned up to dwordx4 (store width is the side the
 // memory system cannot split -- same measured rule as the cast kernels):
-// head dwords to 16-B store alignment, then a uint4-store body fed by
-// align(4) uint4 LOADS -- gfx950 global loads only require dword alignment
-// for dwordx4, so the load side also runs at 16 B/lane even though sample
-// payload starts are only 4-B-granular (the compiler would scalarize to
-// dword loads on targets without unaligned vector access).
-struct __attribute__((aligned(4))) DW4A4 {  // 16-B payload, 4-B alignment
-    uint32_t v[4];
-};
-
-// Copy-body variants for the CSR dword path (selected by DDSTORE_CSR_COPY,
-// A/B evidence in profiles/): 0 = dword loads feeding dwordx4 stores
-// (round-1 shape), 1 = align(4) dwordx4 loads + dwordx4 stores,
-// 2 = variant 1 with nontemporal stores (write-once output bypasses L2).
-template <int VAR>
+// head dwords to 16-B store alignment, then a uint4-store body fed by four
+// dword loads, then the tail dwords. Sample payload starts are only
+// 4-B-granular, so the load side cannot be 16-B aligned as well. Measured
+// against two other bodies (A/B r2, G samples/s): dword loads 1.845,
+// align(4) dwordx4 loads (which gfx950 allows) 1.802, those plus nontemporal
+// stores 1.773 -- wider loads buy nothing here, so the plain ones are used.
 __device__ __forceinline__ void copy_dwords_store16(
     uint32_t* __restrict__ dst, const uint32_t* __restrict__ src,
     int64_t nd, int tid, int nthreads) {
@@ -611,61 +438,49 @@ __device__ __forceinline__ void copy_dwords_store16(
     for (int64_t i = tid; i < h; i += nthreads) dst[i] = src[i];
     const int64_t nb = (nd - h) >> 2;
     uint4* d4 = reinterpret_cast<uint4*>(dst + h);
-    if constexpr (VAR == 0) {
-        const uint32_t* s2 = src + h;
-        for (int64_t i = tid; i < nb; i += nthreads) {
-            uint4 o;
-            o.x = s2[4 * i];
-            o.y = s2[4 * i + 1];
-            o.z = s2[4 * i + 2];
-            o.w = s2[4 * i + 3];
-            d4[i] = o;
-        }
-    } else {
-        const DW4A4* s4 = reinterpret_cast<const DW4A4*>(src + h);
-        for (int64_t i = tid; i < nb; i += nthreads) {
-            const DW4A4 t = s4[i];  // one align(4) dwordx4 load on gfx950
-            uint4 o;
-            o.x = t.v[0];
-            o.y = t.v[1];
-            o.z = t.v[2];
-            o.w = t.v[3];
-            if constexpr (VAR == 2) {
-                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                u32x4 ev = {o.x, o.y, o.z, o.w};
-                __builtin_nontemporal_store(
-                    ev, reinterpret_cast<u32x4*>(&d4[i]));
-            } else {
-                d4[i] = o;
-            }
-        }
+    const uint32_t* s2 = src + h;
+    for (int64_t i = tid; i < nb; i += nthreads) {
+        uint4 o;
+        o.x = s2[4 * i];
+        o.y = s2[4 * i + 1];
+        o.z = s2[4 * i + 2];
+        o.w = s2[4 * i + 3];
+        d4[i] = o;
     }
     for (int64_t i = h + (nb << 2) + tid; i < nd; i += nthreads) dst[i] = src[i];
 }
 
-// CSR gather for 4-B-granular (but not 16-B-aligned) elements: dword
-// addressing with 16-B-aligned stores. GROUP lanes cooperate per sample
-// (16 for small samples so many samples stay in flight per CU, 64 or the
-// whole block for larger payloads).
-template <int GROUP, int VAR>
-__global__ void __launch_bounds__(kBlock)
-k_gather_csr_dw(const void* const* peer_base,
-                const int64_t* sample_prefix, const int64_t* elem_prefix, int nparts,
-                const int64_t* goff,
-                const int64_t* idx, int64_t nidx,
-                const int64_t* out_off, int64_t dwords_per_elem,
-                int64_t cap_elems,
-                uint32_t* __restrict__ out, unsigned long long* ctrs) {
-    __shared__ int64_t s_sprefix[DDS_MAX_PARTS + 1];
-    __shared__ int64_t s_eprefix[DDS_MAX_PARTS + 1];
-    __shared__ const uint32_t* s_base[DDS_MAX_PARTS];
-    for (int i = threadIdx.x; i <= nparts; i += kBlock) {
-        s_sprefix[i] = sample_prefix[i];
-        s_eprefix[i] = elem_prefix[i];
+// Copy n units of type U by `nthreads` cooperating threads: dwords go
+// through the store-aligning copy above, uint4 and bytes one unit per thread.
+template <typename U>
+__device__ __forceinline__ void copy_units(U* dst, const U* src, int64_t n, int tid,
+                                           int nthreads) {
+    if constexpr (std::is_same_v<U, uint32_t>) {
+        copy_dwords_store16(dst, src, n, tid, nthreads);
+    } else {
+        for (int64_t c = tid; c < n; c += nthreads) dst[c] = src[c];
     }
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const uint32_t*>(peer_base[i]);
-    __syncthreads();
+}
+
+// ---------------------------------------------------------------------------
+// CSR gather, per sample: GROUP lanes cooperate per sample (see gather_csr's
+// heuristic note; small groups amortize per-sample setup across the wave --
+// 16 for small samples so many samples stay in flight per CU, 64 or the whole
+// block for larger payloads). U is the copy unit: uint4 for 16-B-granular
+// elements, uint32_t for 4-B-granular ones (dword addressing with
+// 16-B-aligned stores), uint8_t for the rest.
+// ---------------------------------------------------------------------------
+template <typename U, int GROUP>
+__global__ void __launch_bounds__(kBlock)
+k_gather_csr_wave(const void* const* peer_base,
+                  const int64_t* sample_prefix, const int64_t* elem_prefix, int nparts,
+                  const int64_t* goff,
+                  const int64_t* idx, int64_t nidx,
+                  const int64_t* out_off, int64_t units_per_elem,
+                  int64_t cap_elems,
+                  U* __restrict__ out, unsigned long long* ctrs) {
+    __shared__ LdsDir<const U*, 2> dir;
+    dir.load(peer_base, nparts, sample_prefix, elem_prefix);
 
     constexpr int GPB = kBlock / GROUP;  // sample groups per block
     const int64_t first = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP;
@@ -673,25 +488,26 @@ k_gather_csr_dw(const void* const* peer_base,
     const int tid = threadIdx.x % GROUP;
     for (int64_t s = first; s < nidx; s += step) {
         const int64_t g = idx[s];
-        if (g < 0 || g >= s_sprefix[nparts]) {
+        if (out_of_range(dir, nparts, g)) {
             if (tid == 0) atomicAdd(ctrs + DDS_CTR_OOB, 1ull);
             continue;
         }
-        const int p = owner_of(s_sprefix, nparts, g);
+        const int p = owner_of(dir, nparts, g);
         const int64_t e0 = goff[g];
         const int64_t len = goff[g + 1] - e0;
         const int64_t o0 = out_off[s];
-        if (o0 < 0 || o0 + len > cap_elems) {
-            if (tid == 0) {
+        if (o0 < 0 || o0 + len > cap_elems) {  // undersized capacity buffer:
+            if (tid == 0) {                    // never write OOB
                 atomicAdd(ctrs + DDS_CTR_CAP, 1ull);
+                // keep the true-bytes counter honest (see k_csr_plan2)
                 atomicAdd(ctrs + DDS_CTR_ELEMS,
                           (unsigned long long)(-(long long)len));
             }
             continue;
         }
-        copy_dwords_store16<VAR>(out + o0 * dwords_per_elem,
-                                 s_base[p] + (e0 - s_eprefix[p]) * dwords_per_elem,
-                                 len * dwords_per_elem, tid, GROUP);
+        copy_units<U>(out + o0 * units_per_elem,
+                      dir.base[p] + (e0 - dir.prefix[1][p]) * units_per_elem,
+                      len * units_per_elem, tid, GROUP);
     }
 }
 
@@ -920,22 +736,22 @@ k_csr_plan3(const int64_t* __restrict__ lens_tmp,
 // the max-of-N-samples imbalance of the per-sample kernel, and the
 // coalesced 16-B descriptor read is the ONLY metadata access. Item count
 // is read from meta on device (the host never syncs for it).
-template <int GROUP, bool DW, int VAR>
+// U is the descriptors' unit and the copy unit: uint32_t or uint8_t.
+template <typename U, int GROUP>
 __global__ void __launch_bounds__(kBlock)
 k_gather_csr_items(const void* const* peer_base, int nparts,
                    const int64_t* __restrict__ desc,
                    const int64_t* __restrict__ meta,
-                   void* __restrict__ out_, unsigned long long* ctrs) {
-    __shared__ const char* s_base[DDS_MAX_PARTS];
+                   U* __restrict__ out) {
+    __shared__ const U* s_base[DDS_MAX_PARTS];
     for (int i = threadIdx.x; i < nparts; i += kBlock)
-        s_base[i] = reinterpret_cast<const char*>(peer_base[i]);
+        s_base[i] = reinterpret_cast<const U*>(peer_base[i]);
     __syncthreads();
     const int64_t total = meta[0];
     constexpr int GPB = kBlock / GROUP;
     const int64_t first = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP;
     const int64_t step = (int64_t)gridDim.x * GPB;
     const int tid = threadIdx.x % GROUP;
-    (void)ctrs;
     for (int64_t j = first; j < total; j += step) {
         const int64_t d0 = desc[2 * j];
         const int64_t d1 = desc[2 * j + 1];
@@ -943,16 +759,7 @@ k_gather_csr_items(const void* const* peer_base, int nparts,
         const int64_t src_u = d0 & ((int64_t(1) << 56) - 1);
         const int64_t n_u = d1 >> 44;
         const int64_t dst_u = d1 & ((int64_t(1) << 44) - 1);
-        if constexpr (DW) {
-            copy_dwords_store16<VAR>(
-                reinterpret_cast<uint32_t*>(out_) + dst_u,
-                reinterpret_cast<const uint32_t*>(s_base[p]) + src_u,
-                n_u, tid, GROUP);
-        } else {
-            char* dst = reinterpret_cast<char*>(out_) + dst_u;
-            const char* src = s_base[p] + src_u;
-            for (int64_t c = tid; c < n_u; c += GROUP) dst[c] = src[c];
-        }
+        copy_units<U>(out + dst_u, s_base[p] + src_u, n_u, tid, GROUP);
     }
 }
 
@@ -960,14 +767,12 @@ k_gather_csr_items(const void* const* peer_base, int nparts,
 // Local scatter (reshuffle placement): row r of src -> local row
 // local_idx[r] of base. Same chunk mapping as gather.
 // ---------------------------------------------------------------------------
-template <int CHUNK>
+// V is the chunk a thread moves: 32 B, 16 B, or single bytes.
+template <typename V>
 __global__ void __launch_bounds__(kBlock)
-k_scatter_rows_b16(uint4* __restrict__ base_, int64_t nrows, int64_t chunks_per_row,
-                   const int64_t* local_idx, int64_t nidx,
-                   const uint4* __restrict__ src_, unsigned long long* oob) {
-    using V = VecT<uint4, CHUNK / 16>;
-    V* __restrict__ base = reinterpret_cast<V*>(base_);
-    const V* __restrict__ src = reinterpret_cast<const V*>(src_);
+k_scatter_rows(V* __restrict__ base, int64_t nrows, int64_t chunks_per_row,
+               const int64_t* local_idx, int64_t nidx,
+               const V* __restrict__ src, unsigned long long* oob) {
     const int64_t total = nidx * chunks_per_row;
     for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * kBlock) {
@@ -979,25 +784,6 @@ k_scatter_rows_b16(uint4* __restrict__ base_, int64_t nrows, int64_t chunks_per_
             continue;
         }
         base[l * chunks_per_row + c] = src[t];
-    }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-k_scatter_rows_elem(T* __restrict__ base, int64_t nrows, int64_t row_elems,
-                    const int64_t* local_idx, int64_t nidx,
-                    const T* __restrict__ src, unsigned long long* oob) {
-    const int64_t total = nidx * row_elems;
-    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total;
-         t += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = t / row_elems;
-        const int64_t c = t - r * row_elems;
-        const int64_t l = local_idx[r];
-        if (l < 0 || l >= nrows) {
-            if (c == 0) atomicAdd(oob, 1ull);
-            continue;
-        }
-        base[l * row_elems + c] = src[t];
     }
 }
 
@@ -1135,85 +921,65 @@ bool launch_tiled(hipStream_t stream, const DirArgs& d, const int64_t* idx,
     return true;
 }
 
-template <typename Tin, typename Tout>
-void launch_gather_cast_one(hipStream_t stream, const DirArgs& d,
-                            const int64_t* idx,
-                            int64_t n, int64_t re, Tout* out,
-                            unsigned long long* oob) {
+template <typename Tin, typename Tout, int VEC, typename Xf>
+void launch_oneshot(hipStream_t stream, const DirArgs& d, const int64_t* idx,
+                    int64_t n, int64_t re, Xf xf, Tout* out,
+                    unsigned long long* oob) {
+    const int grid = n_blocks(n * (re / VEC));
+    hipLaunchKernelGGL((k_gather_oneshot<Tin, Tout, VEC, Xf>), dim3(grid), dim3(kBlock),
+                       0, stream, d.d_pb, d.d_pf, d.np, idx, n, re, xf, out, oob);
+}
+
+// Cast and affine gathers: tiled if eligible, else the one-shot kernel with
+// 16-B stores if the row and the output pointer allow, else element-wise.
+template <typename Tin, typename Tout, typename Xf>
+void launch_gather(hipStream_t stream, const DirArgs& d, const int64_t* idx,
+                   int64_t n, int64_t re, Xf xf, Tout* out,
+                   unsigned long long* oob) {
     constexpr int VEC = 16 / sizeof(Tout);
-    if (launch_tiled<Tin, Tout>(stream, d, idx, n, re, XfCast{}, out, oob)) return;
-    const void* const* pb = d.d_pb;
-    const int64_t* pf = d.d_pf;
-    const int np = d.np;
-    if (re % VEC == 0 && ((uintptr_t)out % 16) == 0) {
-        const int grid = n_blocks(n * (re / VEC));
-        hipLaunchKernelGGL((k_gather_rows_castv<Tin, Tout>), dim3(grid), dim3(kBlock),
-                           0, stream, pb, pf, np, idx, n, re, out, oob);
-    } else {
-        const int grid = n_blocks(n * re);
-        hipLaunchKernelGGL((k_gather_rows_cast<Tin, Tout>), dim3(grid), dim3(kBlock),
-                           0, stream, pb, pf, np, idx, n, re, out, oob);
+    if (launch_tiled<Tin, Tout>(stream, d, idx, n, re, xf, out, oob)) return;
+    if (re % VEC == 0 && ((uintptr_t)out % 16) == 0)
+        launch_oneshot<Tin, Tout, VEC>(stream, d, idx, n, re, xf, out, oob);
+    else
+        launch_oneshot<Tin, Tout, 1>(stream, d, idx, n, re, xf, out, oob);
+}
+
+// A type handed to a generic lambda as a value.
+template <typename T>
+struct TypeTag {
+    using type = T;
+};
+
+// Calls f(TypeTag<T>{}) with the C++ type of dtype tag `t`; an unknown tag
+// calls nothing.
+template <typename F>
+void dispatch_dtype(int t, F&& f) {
+    switch (t) {
+        case DDS_U8: f(TypeTag<uint8_t>{}); break;
+        case DDS_I32: f(TypeTag<int32_t>{}); break;
+        case DDS_I64: f(TypeTag<int64_t>{}); break;
+        case DDS_F32: f(TypeTag<float>{}); break;
+        case DDS_F64: f(TypeTag<double>{}); break;
+        case DDS_F16: f(TypeTag<__half>{}); break;
+        case DDS_BF16: f(TypeTag<__hip_bfloat16>{}); break;
+        case DDS_F8E4M3: f(TypeTag<__hip_fp8_e4m3>{}); break;
+        case DDS_F8E5M2: f(TypeTag<__hip_fp8_e5m2>{}); break;
     }
 }
 
-template <typename Tin>
-void launch_gather_cast_out(hipStream_t stream, const DirArgs& d,
-                            const int64_t* idx,
-                            int64_t n, int64_t re, int out_t, void* out,
-                            unsigned long long* oob) {
-    switch (out_t) {
-#define DDS_OUT(tag, T)                                                               \
-    case tag:                                                                         \
-        launch_gather_cast_one<Tin, T>(stream, d, idx, n, re, (T*)out, oob);          \
-        break;
-        DDS_OUT(DDS_U8, uint8_t)
-        DDS_OUT(DDS_I32, int32_t)
-        DDS_OUT(DDS_I64, int64_t)
-        DDS_OUT(DDS_F32, float)
-        DDS_OUT(DDS_F64, double)
-        DDS_OUT(DDS_F16, __half)
-        DDS_OUT(DDS_BF16, __hip_bfloat16)
-        DDS_OUT(DDS_F8E4M3, __hip_fp8_e4m3)
-        DDS_OUT(DDS_F8E5M2, __hip_fp8_e5m2)
-#undef DDS_OUT
+// Calls f(std::integral_constant<int, G>{}) for the listed lane-group size G
+// equal to `group`; any other value takes the last one listed.
+template <int G0, int... Gs, typename F>
+void dispatch_group(int group, F&& f) {
+    if constexpr (sizeof...(Gs) == 0) {
+        f(std::integral_constant<int, G0>{});
+    } else {
+        if (group == G0) f(std::integral_constant<int, G0>{});
+        else dispatch_group<Gs...>(group, f);
     }
 }
 
 } // namespace
-
-template <typename Tin>
-void launch_affine_out(hipStream_t stream, const DirArgs& d,
-                       const int64_t* idx, int64_t n, int64_t re,
-                       float a, float b, int out_t, void* out,
-                       unsigned long long* oob) {
-    const void* const* pb = d.d_pb;
-    const int64_t* pf = d.d_pf;
-    const int np = d.np;
-#define DDS_AFF(tag, T)                                                              \
-    case tag: {                                                                      \
-        constexpr int VEC = 16 / sizeof(T);                                          \
-        if (launch_tiled<Tin, T>(stream, d, idx, n, re, XfAffine{a, b}, (T*)out,     \
-                                 oob)) {                                             \
-        } else if (re % VEC == 0 && ((uintptr_t)out % 16) == 0) {                    \
-            const int grid = n_blocks(n * (re / VEC));                               \
-            hipLaunchKernelGGL((k_gather_rows_affine<Tin, T>), dim3(grid),           \
-                               dim3(kBlock), 0, stream, pb, pf, np, idx, n, re, a,   \
-                               b, (T*)out, oob);                                     \
-        } else {                                                                     \
-            const int grid = n_blocks(n * re);                                       \
-            hipLaunchKernelGGL((k_gather_rows_affine_s<Tin, T>), dim3(grid),         \
-                               dim3(kBlock), 0, stream, pb, pf, np, idx, n, re, a,   \
-                               b, (T*)out, oob);                                     \
-        }                                                                            \
-        break;                                                                       \
-    }
-    switch (out_t) {
-        DDS_AFF(DDS_F32, float)
-        DDS_AFF(DDS_F16, __half)
-        DDS_AFF(DDS_BF16, __hip_bfloat16)
-    }
-#undef DDS_AFF
-}
 
 void gather_rows_affine(hipStream_t stream,
                         const void* const* d_peer_base,
@@ -1226,24 +992,17 @@ void gather_rows_affine(hipStream_t stream,
                         void* d_out, unsigned long long* d_oob) {
     if (nidx == 0 || row_elems == 0) return;
     const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
-    switch (in_t) {
-#define DDS_AIN(tag, T)                                                          \
-    case tag:                                                                    \
-        launch_affine_out<T>(stream, dir, d_idx,                                 \
-                             nidx, row_elems, scale, shift, out_t, d_out,        \
-                             d_oob);                                             \
-        break;
-        DDS_AIN(DDS_U8, uint8_t)
-        DDS_AIN(DDS_I32, int32_t)
-        DDS_AIN(DDS_I64, int64_t)
-        DDS_AIN(DDS_F32, float)
-        DDS_AIN(DDS_F64, double)
-        DDS_AIN(DDS_F16, __half)
-        DDS_AIN(DDS_BF16, __hip_bfloat16)
-        DDS_AIN(DDS_F8E4M3, __hip_fp8_e4m3)
-        DDS_AIN(DDS_F8E5M2, __hip_fp8_e5m2)
-#undef DDS_AIN
-    }
+    dispatch_dtype(in_t, [&](auto ti) {
+        dispatch_dtype(out_t, [&](auto to) {
+            using Tin = typename decltype(ti)::type;
+            using Tout = typename decltype(to)::type;
+            // float outputs only
+            if constexpr (std::is_same_v<Tout, float> || std::is_same_v<Tout, __half> ||
+                          std::is_same_v<Tout, __hip_bfloat16>)
+                launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems,
+                                         XfAffine{scale, shift}, (Tout*)d_out, d_oob);
+        });
+    });
 }
 
 void gather_rows(hipStream_t stream,
@@ -1262,7 +1021,6 @@ void gather_rows(hipStream_t stream,
     // whose own vector path re-checks alignment
     const uintptr_t out_align = (uintptr_t)d_out;
     if (in_t == out_t && row_bytes % 16 == 0 && out_align % 16 == 0) {
-        const int64_t cpr = row_bytes / 16;
         // NB: a thread-per-row variant (one idx load, all chunks in flight
         // per thread) was measured SLOWER on MI355X for <=64 B rows (7.5 vs
         // 6.1 us at B=131072): fewer, fatter threads lose more to the
@@ -1281,37 +1039,24 @@ void gather_rows(hipStream_t stream,
         if (launch_tiled<uint32_t, uint32_t>(stream, dir, d_idx, nidx, row_bytes / 4,
                                              XfIdentity{}, (uint32_t*)d_out, d_oob))
             return;
-        if (row_bytes % 32 == 0 && row_bytes >= 128 && out_align % 32 == 0) {
-            const int64_t cpr32 = row_bytes / 32;
-            const int grid = n_blocks(nidx * cpr32);
-            hipLaunchKernelGGL((k_gather_rows_b16<32>), dim3(grid), dim3(kBlock), 0,
-                               stream, d_peer_base, d_prefix, nparts, d_idx, nidx,
-                               cpr32, (uint4*)d_out, d_oob);
-        } else {
-            const int grid = n_blocks(nidx * cpr);
-            hipLaunchKernelGGL((k_gather_rows_b16<16>), dim3(grid), dim3(kBlock), 0,
-                               stream, d_peer_base, d_prefix, nparts, d_idx, nidx,
-                               cpr, (uint4*)d_out, d_oob);
-        }
+        // one 32-B or 16-B vector is the element, so VEC = 1
+        using V32 = VecT<uint4, 2>;
+        if (row_bytes % 32 == 0 && row_bytes >= 128 && out_align % 32 == 0)
+            launch_oneshot<V32, V32, 1>(stream, dir, d_idx, nidx, row_bytes / 32,
+                                        XfIdentity{}, (V32*)d_out, d_oob);
+        else
+            launch_oneshot<uint4, uint4, 1>(stream, dir, d_idx, nidx, row_bytes / 16,
+                                            XfIdentity{}, (uint4*)d_out, d_oob);
         return;
     }
-    switch (in_t) {
-#define DDS_IN(tag, T)                                                           \
-    case tag:                                                                    \
-        launch_gather_cast_out<T>(stream, dir, d_idx,                            \
-                                  nidx, row_elems, out_t, d_out, d_oob);         \
-        break;
-        DDS_IN(DDS_U8, uint8_t)
-        DDS_IN(DDS_I32, int32_t)
-        DDS_IN(DDS_I64, int64_t)
-        DDS_IN(DDS_F32, float)
-        DDS_IN(DDS_F64, double)
-        DDS_IN(DDS_F16, __half)
-        DDS_IN(DDS_BF16, __hip_bfloat16)
-        DDS_IN(DDS_F8E4M3, __hip_fp8_e4m3)
-        DDS_IN(DDS_F8E5M2, __hip_fp8_e5m2)
-#undef DDS_IN
-    }
+    dispatch_dtype(in_t, [&](auto ti) {
+        dispatch_dtype(out_t, [&](auto to) {
+            using Tin = typename decltype(ti)::type;
+            using Tout = typename decltype(to)::type;
+            launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems, XfCast{},
+                                     (Tout*)d_out, d_oob);
+        });
+    });
 }
 
 void csr_lens(hipStream_t stream, const int64_t* d_goff, const int64_t* d_idx,
@@ -1350,53 +1095,27 @@ void gather_csr(hipStream_t stream,
     // vector paths reinterpret d_out; a misaligned output (e.g. an offset
     // view) falls back to the next-narrower granularity
     const uintptr_t oa = (uintptr_t)d_out;
-#define DDS_CSR_G(T, div, G)                                                         \
-    hipLaunchKernelGGL((k_gather_csr_wave<T, G>), dim3(grid), dim3(kBlock), 0,       \
-                       stream, d_peer_base, d_sample_prefix, d_elem_prefix, nparts,  \
-                       d_goff, d_idx, nidx, d_out_off, elem_bytes / div, cap_elems,  \
-                       (T*)d_out, d_ctrs)
-#define DDS_CSR_T(T, div)                                                            \
-    do {                                                                             \
-        if (group == 8) DDS_CSR_G(T, div, 8);                                        \
-        else if (group == 16) DDS_CSR_G(T, div, 16);                                  \
-        else if (group == 32) DDS_CSR_G(T, div, 32);                                 \
-        else if (group == 64) DDS_CSR_G(T, div, 64);                                 \
-        else DDS_CSR_G(T, div, 256);                                                 \
-    } while (0)
-    static const int copy_var = [] {
-        const char* e = getenv("DDSTORE_CSR_COPY");
-        int v = e ? atoi(e) : 0;  // A/B r2: dword loads won (1.845 vs
-        return (v >= 0 && v <= 2) ? v : 0;  // 1.802/1.773 G samples/s)
-    }();
-#define DDS_CSR_DW_V(G, V)                                                           \
-    hipLaunchKernelGGL((k_gather_csr_dw<G, V>), dim3(grid), dim3(kBlock), 0, stream, \
-                       d_peer_base, d_sample_prefix, d_elem_prefix, nparts, d_goff,  \
-                       d_idx, nidx, d_out_off, elem_bytes / 4, cap_elems,            \
-                       (uint32_t*)d_out, d_ctrs)
-#define DDS_CSR_DW(G)                                                                \
-    do {                                                                             \
-        if (copy_var == 0) DDS_CSR_DW_V(G, 0);                                       \
-        else if (copy_var == 2) DDS_CSR_DW_V(G, 2);                                  \
-        else DDS_CSR_DW_V(G, 1);                                                     \
-    } while (0)
+    auto launch = [&](auto unit) {
+        using U = typename decltype(unit)::type;
+        dispatch_group<8, 16, 32, 64, 256>(group, [&](auto G) {
+            hipLaunchKernelGGL((k_gather_csr_wave<U, G()>), dim3(grid), dim3(kBlock), 0,
+                               stream, d_peer_base, d_sample_prefix, d_elem_prefix,
+                               nparts, d_goff, d_idx, nidx, d_out_off,
+                               elem_bytes / (int64_t)sizeof(U), cap_elems, (U*)d_out,
+                               d_ctrs);
+        });
+    };
     if (elem_bytes % 16 == 0 && oa % 16 == 0) {
-        DDS_CSR_T(uint4, 16);
+        launch(TypeTag<uint4>{});
     } else if (elem_bytes % 4 == 0 && oa % 4 == 0) {
         // 4/8-B-granular elements: dword addressing, stores re-aligned to
         // dwordx4 inside each sample's payload
-        if (group == 8) DDS_CSR_DW(8);
-        else if (group == 16) DDS_CSR_DW(16);
-        else if (group == 32) DDS_CSR_DW(32);
-        else if (group == 64) DDS_CSR_DW(64);
-        else DDS_CSR_DW(256);
+        launch(TypeTag<uint32_t>{});
     } else {
-        DDS_CSR_T(uint8_t, 1);
+        launch(TypeTag<uint8_t>{});
     }
-#undef DDS_CSR_G
-#undef DDS_CSR_T
-#undef DDS_CSR_DW
-#undef DDS_CSR_DW_V
 }
+
 size_t csr_plan_scratch_bytes(int64_t nidx) {
     const int64_t ntiles = (nidx + kBlock - 1) / kBlock;
     return (size_t)(2 * (ntiles > 0 ? ntiles : 1) + 2 * (nidx > 0 ? nidx : 1)
@@ -1447,35 +1166,21 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
         int v = e ? atoi(e) : 16;
         return (v == 8 || v == 16 || v == 32) ? v : 16;
     }();
-    static const int item_var = [] {
-        const char* e = getenv("DDSTORE_CSR_COPY");
-        int v = e ? atoi(e) : 0;
-        return (v >= 0 && v <= 2) ? v : 0;
-    }();
     const int64_t gi = (desc_cap + (kBlock / item_group) - 1)
                        / (kBlock / item_group);
     const int g2 = (int)(gi < kMaxBlocks ? gi : kMaxBlocks);
-#define DDS_ITEMS_GV(G, V)                                                     \
-    hipLaunchKernelGGL((k_gather_csr_items<G, true, V>), dim3(g2),             \
-                       dim3(kBlock), 0, stream, d_peer_base, nparts, d_desc,   \
-                       meta, d_out, d_ctrs)
-#define DDS_ITEMS_G(G)                                                         \
-    do {                                                                       \
-        if (item_var == 1) DDS_ITEMS_GV(G, 1);                                 \
-        else if (item_var == 2) DDS_ITEMS_GV(G, 2);                            \
-        else DDS_ITEMS_GV(G, 0);                                               \
-    } while (0)
+    auto launch = [&](auto unit, auto G) {
+        using U = typename decltype(unit)::type;
+        hipLaunchKernelGGL((k_gather_csr_items<U, G()>), dim3(g2), dim3(kBlock), 0,
+                           stream, d_peer_base, nparts, d_desc, meta, (U*)d_out);
+    };
     if (dw) {
-        if (item_group == 8) DDS_ITEMS_G(8);
-        else if (item_group == 32) DDS_ITEMS_G(32);
-        else DDS_ITEMS_G(16);
+        dispatch_group<8, 32, 16>(item_group, [&](auto G) {
+            launch(TypeTag<uint32_t>{}, G);
+        });
     } else {
-        hipLaunchKernelGGL((k_gather_csr_items<16, false, 0>), dim3(g2),
-                           dim3(kBlock), 0, stream, d_peer_base, nparts,
-                           d_desc, meta, d_out, d_ctrs);
+        launch(TypeTag<uint8_t>{}, std::integral_constant<int, 16>{});
     }
-#undef DDS_ITEMS_GV
-#undef DDS_ITEMS_G
 }
 
 void scatter_rows_local(hipStream_t stream,
@@ -1486,25 +1191,19 @@ void scatter_rows_local(hipStream_t stream,
     if (nidx == 0 || row_elems == 0) return;
     const int64_t row_bytes = row_elems * dds_itemsize(elem_t);
     const uintptr_t al = (uintptr_t)d_src | (uintptr_t)d_base;
-    if (row_bytes % 32 == 0 && row_bytes >= 128 && al % 32 == 0) {
-        const int64_t cpr = row_bytes / 32;
-        const int grid = n_blocks(nidx * cpr);
-        hipLaunchKernelGGL((k_scatter_rows_b16<32>), dim3(grid), dim3(kBlock), 0,
-                           stream, (uint4*)d_base, nrows_local, cpr, d_local_idx,
-                           nidx, (const uint4*)d_src, d_oob);
-    } else if (row_bytes % 16 == 0 && al % 16 == 0) {
-        const int64_t cpr = row_bytes / 16;
-        const int grid = n_blocks(nidx * cpr);
-        hipLaunchKernelGGL((k_scatter_rows_b16<16>), dim3(grid), dim3(kBlock), 0,
-                           stream, (uint4*)d_base, nrows_local, cpr, d_local_idx,
-                           nidx, (const uint4*)d_src, d_oob);
-    } else {
-        const int64_t total_bytes = nidx * row_bytes;
-        const int grid = n_blocks(total_bytes);
-        hipLaunchKernelGGL((k_scatter_rows_elem<uint8_t>), dim3(grid), dim3(kBlock), 0,
-                           stream, (uint8_t*)d_base, nrows_local, row_bytes,
-                           d_local_idx, nidx, (const uint8_t*)d_src, d_oob);
-    }
+    auto launch = [&](auto chunk) {
+        using V = typename decltype(chunk)::type;
+        const int64_t cpr = row_bytes / (int64_t)sizeof(V);
+        hipLaunchKernelGGL((k_scatter_rows<V>), dim3(n_blocks(nidx * cpr)),
+                           dim3(kBlock), 0, stream, (V*)d_base, nrows_local, cpr,
+                           d_local_idx, nidx, (const V*)d_src, d_oob);
+    };
+    if (row_bytes % 32 == 0 && row_bytes >= 128 && al % 32 == 0)
+        launch(TypeTag<VecT<uint4, 2>>{});
+    else if (row_bytes % 16 == 0 && al % 16 == 0)
+        launch(TypeTag<uint4>{});
+    else
+        launch(TypeTag<uint8_t>{});
 }
 
 } // namespace ddstore

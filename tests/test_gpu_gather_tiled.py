@@ -103,7 +103,11 @@ def test_tile_edges(store, tin, tout, dim):
 
 
 @pytest.mark.parametrize("tin,tout,dim", [(torch.uint8, torch.bfloat16, 64),
-                                          (torch.float32, torch.float32, 128)],
+                                          (torch.float32, torch.float32, 128),
+                                          # three chunks per row: vector one-shot
+                                          (torch.uint8, torch.bfloat16, 24),
+                                          # 5 % 4 != 0: scalar one-shot
+                                          (torch.float16, torch.float32, 5)],
                          ids=lambda v: str(v).split(".")[-1])
 def test_affine(store, tin, tout, dim):
     # scale and shift have 2 significant bits each, so x * scale + shift in
@@ -117,6 +121,31 @@ def test_affine(store, tin, tout, dim):
         x = dev[idx].to(torch.float32).to(torch.float64)
         exp = (x * scale + shift).to(torch.float32).to(tout)
         assert_bits_equal(out, exp, f"nidx={nidx}")
+
+
+@pytest.mark.parametrize("dim", [32776, 32780])
+def test_rows_above_tiled_limit(store, dim):
+    """Rows of more than 4096 output chunks take the one-shot kernels even by
+    default. dim 32776 (131,104-B rows, a multiple of 32): f32->f32 is 8194
+    16-B chunks and moves 32-B chunks, f32->bf16 is 4097 chunks of the vector
+    cast. dim 32780 (131,120 B, a multiple of 16 only): f32->f32 moves 16-B
+    chunks, f32->bf16 (32780 % 8 != 0) runs the scalar cast."""
+    nrows = 8
+    name = f"wide_{dim}"
+    arr = make_shard(torch.float32, nrows, dim, seed=dim)
+    store.add(name, arr)
+    dev = arr.to("cuda:0")
+    idx = torch.tensor([3, 0, 7, 3, nrows, 5], dtype=torch.int64, device="cuda:0")
+    good = idx < nrows
+    sentinel = -123.0
+    for tout in (torch.float32, torch.bfloat16):
+        out = torch.full((idx.numel(), dim), sentinel, dtype=tout, device="cuda:0")
+        before = store.query(name)["oob_skipped"]
+        store.get_batch(name, idx, out=out)
+        torch.cuda.synchronize()
+        assert (out[~good] == sentinel).all(), f"{tout}: a skipped row was written"
+        assert_bits_equal(out[good], dev[idx[good]].to(tout), f"{tout} valid rows")
+        assert store.query(name)["oob_skipped"] - before == 1
 
 
 def test_special_values_f32_bf16(store):

@@ -239,6 +239,41 @@ def test_csr_elem_widths_gpu(store, disp):
         assert torch.equal(v_h[off_h[k] : off_h[k + 1]], vals[goff[g] : goff[g + 1]])
 
 
+@pytest.mark.parametrize("nidx", [4096, 16384])
+@pytest.mark.parametrize("dtype,disp", [(torch.float32, 4), (torch.float32, 1),
+                                        (torch.uint8, 3)],
+                         ids=["16B", "4B", "3B"])
+def test_csr_per_sample_group_sizes_gpu(store, dtype, disp, nidx):
+    # the per-sample kernel runs 64 lanes per sample from 4096 samples and 16
+    # from 16384 (256 below); 16-B, 4-B and 3-B elements take its uint4,
+    # dword and byte copies
+    rng = np.random.default_rng(nidx + disp)
+    lengths = torch.from_numpy(rng.integers(0, 16, size=2000))
+    total_stored = int(lengths.sum())
+    if dtype == torch.uint8:
+        vals = torch.from_numpy(
+            rng.integers(0, 256, size=(total_stored, disp), dtype=np.uint8))
+    else:
+        vals = torch.randn(total_stored, disp)
+    name = f"pg{nidx}_{disp}"
+    store.add_csr(name, vals, lengths)
+    goff = torch.zeros(2001, dtype=torch.int64)
+    torch.cumsum(lengths, 0, out=goff[1:])
+    idx = torch.from_numpy(rng.integers(0, 2000, size=nidx))
+    lens = lengths[idx]
+    out_off = torch.zeros(nidx + 1, dtype=torch.int64)
+    torch.cumsum(lens, 0, out=out_off[1:])
+    total = int(out_off[-1])
+    out = torch.empty(total, disp, dtype=dtype, device="cuda:0")
+    store._backend.gather_csr(name, idx.cuda(), out_off.cuda(), out, total)
+    torch.cuda.synchronize()
+    # source element of every output element, all samples at once
+    src = torch.repeat_interleave(goff[idx] - out_off[:-1], lens) + torch.arange(total)
+    assert torch.equal(out.cpu(), vals[src])
+    q = store.query(name)
+    assert q["oob_skipped"] == 0 and q["cap_skipped"] == 0, q
+
+
 def test_reshuffle_csr_gpu(store):
     from ddstore_amd.reshuffle import expected_perm
 
