@@ -700,6 +700,47 @@ public:
         return off;
     }
 
+    // Padded CSR fetch: one launch writes the dense (n, max_len, disp)
+    // batch (cast / affine fused, pad broadcast from `pad_bits`, the raw
+    // bits of one output element) and the true per-sample lengths. The
+    // output shape does not depend on the data: no plan, no scratch, no
+    // capacity semantics. True gathered-element stats accumulate in the
+    // device counter block, as for gather_csr_fast.
+    void gather_csr_padded(const std::string& name, const at::Tensor& idx,
+                           at::Tensor out, at::Tensor lengths, int64_t max_len,
+                           int64_t pad_bits, bool affine, double scale,
+                           double shift) {
+        RoctxRange rr_("ddstore::gather_csr_padded");
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.is_csr, "ddstore gather_csr_padded: not a CSR variable");
+        check_peers(v);
+        check_idx(idx);
+        const int64_t nidx = idx.numel();
+        TORCH_CHECK(max_len >= 1, "ddstore gather_csr_padded: max_len must be >= 1");
+        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
+                        out.device().index() == device_,
+                    "ddstore gather_csr_padded: output must be a contiguous tensor "
+                    "on the store device");
+        TORCH_CHECK(out.numel() == nidx * max_len * v.row_elems,
+                    "ddstore gather_csr_padded: shape mismatch");
+        TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.is_contiguous() &&
+                        lengths.device().is_cuda() &&
+                        lengths.device().index() == device_ &&
+                        lengths.numel() == nidx,
+                    "ddstore gather_csr_padded: bad lengths tensor");
+        const int out_t = dds_type_of(out);
+        TORCH_CHECK(!affine || out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
+                    "ddstore gather_csr_padded: affine output must be f32/f16/bf16");
+        ddstore::gather_csr_padded(
+            stream(), (const void* const*)v.d_peers, v.d_prefix, v.d_elem_prefix,
+            nparts_, v.d_goff, v.prefix[nparts_], idx.data_ptr<int64_t>(), nidx,
+            v.row_elems, max_len, v.dds_t, out_t, affine, (float)scale, (float)shift,
+            (uint64_t)pad_bits, out.data_ptr(), lengths.data_ptr<int64_t>(), v.d_oob);
+        v.n_gather += 1;
+        v.rows_gathered += nidx;
+        // bytes accounted via the device DDS_CTR_ELEMS counter (see query)
+    }
+
     void csr_lens(const std::string& name, const at::Tensor& idx, at::Tensor lens) {
         DeviceVar& v = var(name);
         TORCH_CHECK(v.is_csr, "ddstore csr_lens: not a CSR variable");

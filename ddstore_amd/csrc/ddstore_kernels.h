@@ -137,6 +137,27 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
                          unsigned long long* d_ctrs,
                          void* d_scratch, int64_t* d_desc, int64_t desc_cap);
 
+// Padded CSR gather, ONE launch: sample d_idx[s] is written to row s of a
+// dense (nidx, max_len, row_elems) output of dtype `out_t` -- its first
+// min(len, max_len) elements through the byte move / cast / affine
+// (affine: out = cast(in) * scale + shift, f32 math, f32/f16/bf16 outputs
+// only), the rest of the row filled with the pad. `pad_bits` holds the raw
+// bits of ONE output element in its low bytes; the kernel broadcasts them
+// and applies neither cast nor affine to them. d_lengths[s] receives the
+// true stored length (not clipped to max_len). An out-of-range index gives
+// an all-pad row, length 0, and one count in d_ctrs[DDS_CTR_OOB]. The true
+// gathered elements, sum(min(len, max_len)), accumulate into
+// d_ctrs[DDS_CTR_ELEMS]. Every output element is written exactly once; no
+// scratch, no host reads of device data. Directory arguments as gather_csr.
+void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
+                       const int64_t* d_sample_prefix,
+                       const int64_t* d_elem_prefix, int nparts,
+                       const int64_t* d_goff, int64_t nsamples_total,
+                       const int64_t* d_idx, int64_t nidx,
+                       int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                       bool affine, float scale, float shift, uint64_t pad_bits,
+                       void* d_out, int64_t* d_lengths,
+                       unsigned long long* d_ctrs);
 
 // Scatter rows of a packed buffer into the local shard at arbitrary local row
 // ids (inverse of gather_rows with nparts==1). Used by the epoch reshuffle to

@@ -763,6 +763,168 @@ k_gather_csr_items(const void* const* peer_base, int nparts,
     }
 }
 
+// Stats of one padded CSR gather: gathered elements, sum(min(len, max_len)),
+// into DDS_CTR_ELEMS and bad indices into DDS_CTR_OOB. Only the first
+// kPadCountBlocks blocks of the launch run this, each over a strided share of
+// ALL the indices, so a launch issues at most kPadCountBlocks atomics per
+// counter however large its grid is. One atomic per block of the gather grid
+// is not few enough: same-address atomics serialize (plan3 note above), and
+// at the CSR bench shape (B=262144: 32768 blocks, ~43 ns per atomic) they
+// alone held the kernel at 1.40-1.45 ms, whatever the payload mapping and
+// store flavour; with this pre-pass the same kernel takes 149 us (MI355X).
+// The cost is a second read of idx and the two offsets by 64 blocks.
+constexpr int kPadCountBlocks = 64;
+
+template <typename P>
+__device__ __forceinline__ void count_padded(const LdsDir<P, 2>& dir, int nparts,
+                                             const int64_t* goff, const int64_t* idx,
+                                             int64_t nidx, int64_t max_len,
+                                             unsigned long long* s_acc,
+                                             unsigned long long* ctrs) {
+    const int64_t nb = gridDim.x < (unsigned)kPadCountBlocks ? gridDim.x : kPadCountBlocks;
+    unsigned long long acc_elems = 0, acc_oob = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nidx;
+         i += nb * kBlock) {
+        const int64_t g = idx[i];
+        if (out_of_range(dir, nparts, g)) {
+            acc_oob += 1;
+        } else {
+            const int64_t len = goff[g + 1] - goff[g];
+            acc_elems += (unsigned long long)(len < max_len ? len : max_len);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_elems += __shfl_down(acc_elems, off);
+        acc_oob += __shfl_down(acc_oob, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_acc[2 * (threadIdx.x >> 6)] = acc_elems;
+        s_acc[2 * (threadIdx.x >> 6) + 1] = acc_oob;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long e = 0, o = 0;
+        for (int w = 0; w < kBlock / 64; ++w) {
+            e += s_acc[2 * w];
+            o += s_acc[2 * w + 1];
+        }
+        if (e) atomicAdd(ctrs + DDS_CTR_ELEMS, e);
+        if (o) atomicAdd(ctrs + DDS_CTR_OOB, o);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Padded CSR gather: sample idx[s] lands in row s of a dense (n, max_len,
+// disp) output, cut to its first max_len elements and filled up with the pad;
+// lengths[s] gets its true (uncut) length. The output offsets are s * max_len
+// by construction, so there is no scan, no plan and no scratch: one launch.
+//
+// Mapping: lane-groups per sample, as in k_gather_csr_wave -- 2^lg_group
+// lanes own one output row, resolve the sample ONCE (index, the two offsets,
+// owner, source address) and sweep the row's VEC-element chunks with adds
+// only. Chosen by construction over one chunk per thread on the flat output
+// (k_gather_oneshot's mapping), where every thread pays the i64 divide, three
+// dependent metadata loads and the LDS search for ONE chunk; the two were NOT
+// ranked by an A/B -- a first chunk-per-thread version was measured only
+// with per-block counter atomics, which hid everything else (see
+// count_padded). Rows are all the same size on the store side, the side that
+// costs, so the per-sample kernel's max-of-N imbalance does not come back:
+// only the loads differ per row. The group is sized from the chunks per row
+// by the host (8..64 lanes, the whole block for few long rows).
+//
+// Measured on MI355X at the CSR bench shape (B=262144, L=240, disp=1 f32,
+// lengths 16..239: 133.7 MB payload, 251.7 MB f32 output): 149 us f32->f32
+// (2.59 TB/s r+w), 120 us f32->bf16, against 96 us for the ragged get_csr
+// fast path and 13.3 ms for get_csr + torch scatter (+ cast) into the same
+// layout (profiles/csr_padded_ab.txt). Nontemporal 16-B stores (store_out)
+// made no difference here -- 148.8/149.1 us against 148.0/149.2 plain,
+// 120.4/120.9 against 121.0/120.8 for bf16 -- so the stores are plain.
+//
+// VEC = 16 / sizeof(Tout) keeps the store side at 16 B (store-width note at
+// k_gather_oneshot). `aligned` (disp % VEC == 0): no chunk straddles the
+// valid/pad boundary and source chunks are aligned (shard bases come from
+// hipMalloc), so a valid chunk is one vector load. Otherwise, if the ROW
+// still is a whole number of chunks, a chunk is fed by VEC element loads,
+// predicated at the boundary -- 16-B stores from narrower loads, the
+// arrangement copy_dwords_store16 measured best for 4-B-granular payloads;
+// this is what the CSR bench shape (disp = 1) runs. VEC = 1 is the
+// element-wise fallback, and the same-dtype byte move of 16-B-granular
+// elements runs as XfIdentity with VEC = 1 over uint4 units. Pad chunks
+// issue no load. `pad16` holds the pad's raw bits replicated over 16 B; it
+// goes through neither cast nor affine.
+//
+// Stats: the first kPadCountBlocks blocks count before they gather (see
+// count_padded); the gather loop itself touches no counter.
+// ---------------------------------------------------------------------------
+template <typename Tin, typename Tout, int VEC, typename Xf>
+__global__ void __launch_bounds__(kBlock)
+k_gather_csr_padded(const void* const* peer_base, const int64_t* sample_prefix,
+                    const int64_t* elem_prefix, int nparts, const int64_t* goff,
+                    const int64_t* idx, int64_t nidx, int64_t disp, int64_t max_len,
+                    int lg_group, bool aligned, Xf xf, dds_u32x4 pad16,
+                    Tout* __restrict__ out, int64_t* __restrict__ lengths,
+                    unsigned long long* ctrs) {
+    using Vin = VecT<Tin, VEC>;
+    using Vout = VecT<Tout, VEC>;
+    static_assert(sizeof(Vout) <= 16, "pad16 covers one output chunk");
+    __shared__ LdsDir<const Tin*, 2> dir;
+    __shared__ unsigned long long s_acc[2 * (kBlock / 64)];
+    dir.load(peer_base, nparts, sample_prefix, elem_prefix);
+
+    Vout vpad;
+    __builtin_memcpy(&vpad, &pad16, sizeof(Vout));
+    const int group = 1 << lg_group;
+    const int tid = threadIdx.x & (group - 1);
+    const int64_t first =
+        (int64_t)blockIdx.x * (kBlock >> lg_group) + (threadIdx.x >> lg_group);
+    const int64_t step = (int64_t)gridDim.x * (kBlock >> lg_group);
+    const int64_t row_elems = max_len * disp;
+    const int64_t cpr = row_elems / VEC;  // chunks per output row
+    if (blockIdx.x < kPadCountBlocks)  // block-uniform
+        count_padded(dir, nparts, goff, idx, nidx, max_len, s_acc, ctrs);
+    for (int64_t s = first; s < nidx; s += step) {
+        const int64_t g = idx[s];
+        const Tin* sp = nullptr;
+        int64_t nvalid = 0;  // valid elements at the head of the row
+        if (out_of_range(dir, nparts, g)) {  // all-pad row, never read OOB
+            if (tid == 0) lengths[s] = 0;
+        } else {
+            const int p = owner_of(dir, nparts, g);
+            const int64_t e0 = goff[g];
+            const int64_t len = goff[g + 1] - e0;
+            const int64_t take = len < max_len ? len : max_len;
+            sp = dir.base[p] + (e0 - dir.prefix[1][p]) * disp;
+            nvalid = take * disp;
+            if (tid == 0) lengths[s] = len;
+        }
+        Vout* __restrict__ op = reinterpret_cast<Vout*>(out + s * row_elems);
+        for (int64_t c = tid; c < cpr; c += group) {
+            const int64_t e = c * VEC;
+            Vout vout = vpad;
+            if (e < nvalid) {
+                if (VEC == 1 || aligned) {
+                    const Vin vin = *reinterpret_cast<const Vin*>(sp + e);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k)
+                        vout.v[k] = xf.template apply<Tout>(vin.v[k]);
+                } else if (e + VEC <= nvalid) {
+                    Tin x[VEC];
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) x[k] = sp[e + k];
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k)
+                        vout.v[k] = xf.template apply<Tout>(x[k]);
+                } else {  // the chunk on the valid/pad boundary
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k)
+                        if (e + k < nvalid) vout.v[k] = xf.template apply<Tout>(sp[e + k]);
+                }
+            }
+            op[c] = vout;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Local scatter (reshuffle placement): row r of src -> local row
 // local_idx[r] of base. Same chunk mapping as gather.
@@ -1114,6 +1276,81 @@ void gather_csr(hipStream_t stream,
     } else {
         launch(TypeTag<uint8_t>{});
     }
+}
+
+void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
+                       const int64_t* d_sample_prefix,
+                       const int64_t* d_elem_prefix, int nparts,
+                       const int64_t* d_goff, int64_t nsamples_total,
+                       const int64_t* d_idx, int64_t nidx,
+                       int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                       bool affine, float scale, float shift, uint64_t pad_bits,
+                       void* d_out, int64_t* d_lengths,
+                       unsigned long long* d_ctrs) {
+    if (nidx == 0) return;
+    if (row_elems == 0 || max_len == 0) {
+        // no payload to move: lengths and the bad-index count only
+        hipLaunchKernelGGL(k_csr_lens, dim3(n_blocks(nidx)), dim3(kBlock), 0, stream,
+                           d_goff, d_idx, nidx, nsamples_total, d_lengths,
+                           d_ctrs + DDS_CTR_OOB, (unsigned long long*)nullptr);
+        return;
+    }
+    // the pad's raw bits, replicated over one 16-B output chunk
+    const int osz = dds_itemsize(out_t);
+    unsigned char pb[16];
+    for (int i = 0; i < 16; ++i) pb[i] = (unsigned char)(pad_bits >> (8 * (i % osz)));
+    dds_u32x4 pad16;
+    __builtin_memcpy(&pad16, pb, 16);
+    const uintptr_t oa = (uintptr_t)d_out;
+    // `disp` counts Tin/Tout units per element
+    auto launch = [&](auto ti, auto to, auto vec, auto xf, int64_t disp, bool aligned) {
+        using Tin = typename decltype(ti)::type;
+        using Tout = typename decltype(to)::type;
+        constexpr int VEC = decltype(vec)::value;
+        // lanes per row: the chunks of one row, 8..64; the whole block for
+        // few long rows (chip coverage, as in gather_csr)
+        const int64_t cpr = max_len * disp / VEC;
+        int lg = cpr <= 8 ? 3 : (cpr <= 16 ? 4 : (cpr <= 32 ? 5 : 6));
+        if (cpr > 64 && nidx < 4096) lg = 8;
+        const int64_t gpb = kBlock >> lg;
+        const int64_t b = (nidx + gpb - 1) / gpb;
+        hipLaunchKernelGGL((k_gather_csr_padded<Tin, Tout, VEC, decltype(xf)>),
+                           dim3((unsigned)(b < kMaxBlocks ? b : kMaxBlocks)),
+                           dim3(kBlock), 0, stream, d_peer_base, d_sample_prefix,
+                           d_elem_prefix, nparts, d_goff, d_idx, nidx, disp, max_len,
+                           lg, aligned, xf, pad16, (Tout*)d_out, d_lengths, d_ctrs);
+    };
+    const int64_t elem_bytes = row_elems * dds_itemsize(in_t);
+    if (!affine && in_t == out_t && elem_bytes % 16 == 0 && oa % 16 == 0) {
+        // byte move: one uint4 is the unit, so VEC = 1
+        launch(TypeTag<uint4>{}, TypeTag<uint4>{}, std::integral_constant<int, 1>{},
+               XfIdentity{}, elem_bytes / 16, true);
+        return;
+    }
+    // 16-B stores if the output pointer and the row allow (vector loads if
+    // the element width allows as well), else element-wise
+    auto launch_xf = [&](auto ti, auto to, auto xf) {
+        using Tout = typename decltype(to)::type;
+        constexpr int VEC = 16 / sizeof(Tout);
+        if (oa % 16 == 0 && (max_len * row_elems) % VEC == 0)
+            launch(ti, to, std::integral_constant<int, VEC>{}, xf, row_elems,
+                   row_elems % VEC == 0);
+        else
+            launch(ti, to, std::integral_constant<int, 1>{}, xf, row_elems, true);
+    };
+    dispatch_dtype(in_t, [&](auto ti) {
+        dispatch_dtype(out_t, [&](auto to) {
+            using Tout = typename decltype(to)::type;
+            if (!affine) {
+                launch_xf(ti, to, XfCast{});
+            } else if constexpr (std::is_same_v<Tout, float> ||
+                                 std::is_same_v<Tout, __half> ||
+                                 std::is_same_v<Tout, __hip_bfloat16>) {
+                // float outputs only
+                launch_xf(ti, to, XfAffine{scale, shift});
+            }
+        });
+    });
 }
 
 size_t csr_plan_scratch_bytes(int64_t nidx) {

@@ -44,6 +44,11 @@ class PrefetchLoader:
     label_name : optional second variable gathered with the same indices
     depth : int           ring depth (2 = classic double buffering)
     drop_last : bool
+    pad_to : optional int CSR variables only: fetch fixed-shape padded batches
+                          with ``get_csr_padded(max_len=pad_to)``; each batch
+                          is ``(dense, lengths)`` instead of ``(values,
+                          offsets)``, and ``out_dtype``/``affine`` are honoured
+    pad_value :           fill for positions past a sample's length
     """
 
     def __init__(
@@ -59,6 +64,8 @@ class PrefetchLoader:
         drop_last: bool = False,
         affine: Optional[tuple] = None,
         collect_events: bool = False,
+        pad_to: Optional[int] = None,
+        pad_value=0,
     ):
         # collect_events=True records (start, end) CUDA events around every
         # side-stream fetch into self.fetch_events -- overlap instrumentation
@@ -80,8 +87,15 @@ class PrefetchLoader:
         idx = torch.as_tensor(indices, dtype=torch.int64).flatten()
         self.indices = idx
         self.is_csr = store._meta(name)["is_csr"]
+        self.pad_to = None if pad_to is None else int(pad_to)
+        self.pad_value = pad_value
+        if self.pad_to is not None:
+            if not self.is_csr:
+                raise ValueError("pad_to is only supported for CSR variables")
+            if self.pad_to < 1:
+                raise ValueError("pad_to must be >= 1")
         if self.is_csr:
-            if affine is not None:
+            if affine is not None and self.pad_to is None:
                 raise ValueError("affine is not supported for CSR variables")
             if label_name is not None and store._meta(label_name)["is_csr"]:
                 raise ValueError("label variable must be fixed-stride")
@@ -99,9 +113,22 @@ class PrefetchLoader:
         return [idx[i : min(i + self.batch_size, stop)] for i in range(0, stop, self.batch_size)]
 
     def _fetch(self, b: torch.Tensor, slot: Optional[dict] = None):
-        """One batch fetch; CSR variables yield (values, offsets) tuples."""
+        """One batch fetch; CSR variables yield (values, offsets) tuples, or
+        (dense, lengths) with ``pad_to``."""
         store = self.store
-        if self.is_csr:
+        if self.is_csr and self.pad_to is not None:
+            meta = store._meta(self.name)
+            shape = (b.numel(), self.pad_to, meta["disp"])
+            buf = None if slot is None else slot.get("data")
+            if buf is not None and buf.shape != shape:
+                buf = None  # ragged final batch: allocate a matching buffer
+            if buf is None:
+                buf = torch.empty(shape, dtype=self.out_dtype or meta["dtype"],
+                                  device=store.device)
+            data = store.get_csr_padded(self.name, b, self.pad_to, out=buf,
+                                        affine=self.affine,
+                                        pad_value=self.pad_value)
+        elif self.is_csr:
             cap = b.numel() * self._max_len
             buf = None if slot is None else slot.get("data")
             if buf is None or buf.shape[0] < cap:

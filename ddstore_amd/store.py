@@ -432,6 +432,100 @@ class DDStore:
         self._backend.gather_csr(name, idx, out_off, out, total)
         return out, out_off
 
+    def get_csr_padded(
+        self,
+        name: str,
+        indices: ArrayLike,
+        max_len: int,
+        out: Optional[torch.Tensor] = None,
+        dtype: Optional[torch.dtype] = None,
+        affine: Optional[Tuple[float, float]] = None,
+        pad_value=0,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Gather variable-length samples into a fixed-shape batch; returns
+        ``(dense, lengths)``.
+
+        ``dense`` is ``(n, max_len, disp)``: ``dense[i, j]`` is element ``j``
+        of sample ``indices[i]``, byte-moved, cast to ``dtype`` or run through
+        ``affine=(scale, shift)`` exactly as :meth:`get_batch` does; positions
+        ``j >= len_i`` hold ``pad_value`` (converted once to the output dtype,
+        never cast or scaled). ``lengths`` is int64 ``(n,)`` with the TRUE
+        stored length of each sample: a sample longer than ``max_len`` is
+        truncated to its first ``max_len`` elements, which the caller detects
+        with ``lengths > max_len`` (masks: ``lengths.clamp(max=max_len)``).
+        An out-of-range index gives an all-pad row of length 0 and is counted
+        in ``query()["oob_skipped"]``. On the GPU this is one kernel launch:
+        no scan, no scratch, no host sync, every element written once."""
+        meta = self._meta(name)
+        if not meta["is_csr"]:
+            raise ValueError(f"ddstore get_csr_padded: '{name}' is not a CSR variable")
+        max_len = int(max_len)
+        if max_len < 1:
+            raise ValueError("ddstore get_csr_padded: max_len must be >= 1")
+        idx = torch.as_tensor(indices, dtype=torch.int64).flatten()
+        idx = idx.to(self.device, non_blocking=True).contiguous()
+        n, disp = idx.numel(), meta["disp"]
+        out_dtype = dtype or (out.dtype if out is not None else meta["dtype"])
+        if out is not None:
+            if (not out.is_contiguous() or out.device != self.device
+                    or out.dtype != out_dtype or out.numel() != n * max_len * disp):
+                raise ValueError(
+                    "ddstore get_csr_padded: out must be a contiguous "
+                    f"{out_dtype} tensor of {n}*{max_len}*{disp} elements on "
+                    "the store device")
+        if affine is not None:
+            scale, shift = float(affine[0]), float(affine[1])
+            if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                raise TypeError("ddstore get_csr_padded: affine output must be float")
+        pad = torch.tensor([pad_value], dtype=out_dtype)  # converted once, on the host
+        if n == 0:
+            dense = out if out is not None else torch.empty(
+                (0, max_len, disp), dtype=out_dtype, device=self.device)
+            return (dense.view(0, max_len, disp),
+                    torch.empty(0, dtype=torch.int64, device=self.device))
+        self._account(meta, idx)
+        if self.mode == "hip":
+            dense = out if out is not None else torch.empty(
+                (n, max_len, disp), dtype=out_dtype, device=self.device)
+            lengths = torch.empty(n, dtype=torch.int64, device=self.device)
+            # the pad travels as the raw bits of one output element
+            bits_t = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+            pad_bits = int(pad.view(bits_t[pad.element_size()]).item())
+            if affine is not None:
+                self._backend.gather_csr_padded(name, idx, dense, lengths, max_len,
+                                                pad_bits, True, scale, shift)
+            else:
+                self._backend.gather_csr_padded(name, idx, dense, lengths, max_len,
+                                                pad_bits)
+            return dense.view(n, max_len, disp), lengths
+        # host path: ragged gather (skips and counts a bad index), then one
+        # masked take into the dense layout -- each element written once
+        goff = meta["goff"]
+        ok = (idx >= 0) & (idx < meta["nrows_total"])
+        safe = torch.where(ok, idx, torch.zeros_like(idx))
+        lengths = torch.where(ok, goff[safe + 1] - goff[safe], torch.zeros_like(idx))
+        off = torch.zeros(n + 1, dtype=torch.int64)
+        torch.cumsum(lengths, 0, out=off[1:])
+        total = int(off[-1].item())
+        vals = torch.empty((total, disp), dtype=meta["dtype"])
+        self._backend.gather_csr(name, idx, off, vals, total)
+        pos = torch.arange(max_len, dtype=torch.int64)
+        valid = pos.unsqueeze(0) < lengths.clamp(max=max_len).unsqueeze(1)
+        src = (off[:-1].unsqueeze(1) + pos.unsqueeze(0)).clamp(max=max(total - 1, 0))
+        if total > 0:
+            x = vals[src]  # (n, max_len, disp); pad positions masked below
+            if affine is not None:
+                x = (x.to(torch.float32) * scale + shift).to(out_dtype)
+            elif x.dtype != out_dtype:
+                x = x.to(out_dtype)
+            dense_v = torch.where(valid.unsqueeze(2), x, pad)
+        else:
+            dense_v = pad.expand(n, max_len, disp)
+        if out is None:
+            return dense_v.contiguous(), lengths
+        out.view(n, max_len, disp).copy_(dense_v)
+        return out.view(n, max_len, disp), lengths
+
     def local_shard(self, name: str) -> torch.Tensor:
         """Zero-copy view of this rank's shard (rows x disp). Valid until
         ``free``."""
