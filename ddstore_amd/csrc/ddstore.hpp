@@ -687,7 +687,9 @@ public:
             {(int64_t)ddstore::csr_plan_scratch_bytes(nidx)}, bopts);
         const int64_t desc_cap =
             cap / ddstore::csr_item_elems(elem_bytes) + nidx;
-        at::Tensor desc = at::empty({2 * desc_cap}, opts);  // 2 i64 per item
+        // 2 i64 per item; uninitialised on purpose: the gather only acts on
+        // slots the plan wrote in this call (see gather_csr_balanced)
+        at::Tensor desc = at::empty({2 * desc_cap}, opts);
         ddstore::gather_csr_balanced(
             stream(), (const void* const*)v.d_peers, v.d_prefix,
             v.d_elem_prefix, nparts_, v.d_goff, v.prefix[nparts_],
@@ -1247,6 +1249,7 @@ public:
                 }
                 int p = owner_of_host(v.prefix, g);
                 int64_t e0 = go[g], n = go[g + 1] - go[g];
+                if (n <= 0) continue;  // an empty sample: nothing to write or skip
                 if (oo[s] < 0 || oo[s] + n > cap) {
                     ++my_cap;
                     continue;

@@ -94,8 +94,9 @@ void gather_rows_affine(hipStream_t stream,
 // [d_goff[g], d_goff[g+1]) of the global element space; each element is
 // `elem_bytes` bytes (= disp * itemsize). Output element offsets per sample
 // are provided in d_out_off (exclusive scan, [nidx+1]). `cap_elems` is the
-// output buffer's capacity in elements: a sample whose slice would end past
-// it is SKIPPED and counted in d_ctrs[DDS_CTR_CAP] (never written OOB).
+// output buffer's capacity in elements: a non-empty sample whose slice would
+// end past it is SKIPPED and counted in d_ctrs[DDS_CTR_CAP] (never written
+// OOB). An empty sample writes nothing and is never counted.
 //   d_sample_prefix : array[nparts+1] -- per-rank sample-count prefix sums
 //   d_elem_prefix   : array[nparts+1] -- per-rank element-count prefix sums
 void gather_csr(hipStream_t stream,
@@ -121,10 +122,16 @@ void csr_lens(hipStream_t stream, const int64_t* d_goff, const int64_t* d_idx,
 // gather waves get near-uniform work (the per-sample kernel loses ~1.5x to
 // max-of-N-samples-per-wave imbalance; r2 fixed-len A/B). Writes
 // d_out_off[nidx+1]; accumulates true gathered elements into
-// d_ctrs[DDS_CTR_ELEMS]; over-capacity samples are skipped + counted.
+// d_ctrs[DDS_CTR_ELEMS]. A sample with L > 0 elements whose slice would end
+// past cap_elems is skipped: nothing of it is written, it counts once in
+// d_ctrs[DDS_CTR_CAP], and d_out_off still carries the unclamped scan. A
+// zero-length sample writes nothing and is never counted.
 // d_scratch: csr_plan_scratch_bytes(nidx) bytes (no zeroing needed);
-// d_desc: int64 work-item descriptors, capacity
-// cap_elems / csr_item_elems(elem_bytes) + nidx entries.
+// d_desc: desc_cap work-item descriptors of 2 int64 each, desc_cap =
+// cap_elems / csr_item_elems(elem_bytes) + nidx, no zeroing needed either:
+// the gather acts only on slots below min(item total, desc_cap), and the plan
+// writes every one of them in the same call (zero-length for the slots of
+// skipped samples), whatever the buffer held before.
 size_t csr_plan_scratch_bytes(int64_t nidx);
 int64_t csr_item_elems(int64_t elem_bytes);
 void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,

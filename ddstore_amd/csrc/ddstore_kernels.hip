@@ -496,6 +496,7 @@ k_gather_csr_wave(const void* const* peer_base,
         const int64_t e0 = goff[g];
         const int64_t len = goff[g + 1] - e0;
         const int64_t o0 = out_off[s];
+        if (len <= 0) continue;  // an empty sample: nothing to write or skip
         if (o0 < 0 || o0 + len > cap_elems) {  // undersized capacity buffer:
             if (tid == 0) {                    // never write OOB
                 atomicAdd(ctrs + DDS_CTR_CAP, 1ull);
@@ -667,6 +668,13 @@ k_csr_plan2(int64_t* __restrict__ aggs, int64_t ntiles,
 // were measured to cost MORE than the imbalance they fixed: 110 vs 75 us):
 //   desc[2j]   = (peer << 56) | src_unit_offset   (units: dwords or bytes)
 //   desc[2j+1] = (n_units << 44) | dst_unit_offset
+// Contract with k_gather_csr_items: desc is uninitialised memory, and the
+// item total in meta[0] (scanned before the capacity check) counts the slots
+// of skipped samples too. So every slot j < min(meta[0], desc_cap) is written
+// here in the same call -- a kept sample's pieces, or (0, 0) = zero units for
+// a skipped one -- and the gather reads no slot at or beyond that bound. A
+// kept sample's slots always lie below desc_cap (sum of ceil(L / item_elems)
+// over samples that fit cap_elems <= cap_elems / item_elems + nidx).
 __global__ void __launch_bounds__(kBlock)
 k_csr_plan3(const int64_t* __restrict__ lens_tmp,
             const int64_t* __restrict__ e0_tmp, int64_t nidx,
@@ -705,11 +713,19 @@ k_csr_plan3(const int64_t* __restrict__ lens_tmp,
                 if (excl_e + L > cap_elems ||
                     excl_i + items > desc_cap ||
                     L * units_per_elem >= (int64_t(1) << 44)) {
-                    // over-capacity (or pathological): no items emitted,
-                    // never written out of bounds; counted
+                    // over-capacity (or pathological): nothing of the
+                    // sample is written; counted. Its slots are still part
+                    // of the scanned item total, so those below desc_cap
+                    // get zero-length descriptors (see the contract above)
                     atomicAdd(ctrs + DDS_CTR_CAP, 1ull);
                     atomicAdd(ctrs + DDS_CTR_ELEMS,
                               (unsigned long long)(-(long long)L));
+                    const int64_t end =
+                        items < desc_cap - excl_i ? excl_i + items : desc_cap;
+                    for (int64_t j = excl_i; j < end; ++j) {
+                        desc[2 * j] = 0;
+                        desc[2 * j + 1] = 0;
+                    }
                 } else {
                     const int64_t g = idx[i];
                     const int64_t p = owner_of(s_sprefix, nparts, g);
@@ -735,19 +751,21 @@ k_csr_plan3(const int64_t* __restrict__ lens_tmp,
 // one sample, self-contained descriptor); near-uniform work per wave kills
 // the max-of-N-samples imbalance of the per-sample kernel, and the
 // coalesced 16-B descriptor read is the ONLY metadata access. Item count
-// is read from meta on device (the host never syncs for it).
+// is read from meta on device (the host never syncs for it) and bounded by
+// desc_cap: with skipped samples it can exceed the slots that exist, and
+// only slots below min(meta[0], desc_cap) were written by k_csr_plan3.
 // U is the descriptors' unit and the copy unit: uint32_t or uint8_t.
 template <typename U, int GROUP>
 __global__ void __launch_bounds__(kBlock)
 k_gather_csr_items(const void* const* peer_base, int nparts,
                    const int64_t* __restrict__ desc,
-                   const int64_t* __restrict__ meta,
+                   const int64_t* __restrict__ meta, int64_t desc_cap,
                    U* __restrict__ out) {
     __shared__ const U* s_base[DDS_MAX_PARTS];
     for (int i = threadIdx.x; i < nparts; i += kBlock)
         s_base[i] = reinterpret_cast<const U*>(peer_base[i]);
     __syncthreads();
-    const int64_t total = meta[0];
+    const int64_t total = meta[0] < desc_cap ? meta[0] : desc_cap;
     constexpr int GPB = kBlock / GROUP;
     const int64_t first = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP;
     const int64_t step = (int64_t)gridDim.x * GPB;
@@ -1409,7 +1427,8 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
     auto launch = [&](auto unit, auto G) {
         using U = typename decltype(unit)::type;
         hipLaunchKernelGGL((k_gather_csr_items<U, G()>), dim3(g2), dim3(kBlock), 0,
-                           stream, d_peer_base, nparts, d_desc, meta, (U*)d_out);
+                           stream, d_peer_base, nparts, d_desc, meta, desc_cap,
+                           (U*)d_out);
     };
     if (dw) {
         dispatch_group<8, 32, 16>(item_group, [&](auto G) {

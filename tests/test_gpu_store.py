@@ -476,13 +476,18 @@ def test_csr_capacity_clamp_gpu(store):
     vals = torch.arange(16, dtype=torch.float32).reshape(16, 1)
     store.add_csr("clamp", vals, lens)
     guard = torch.full((64,), -7.0, device="cuda:0")  # heap canary after out
-    out = torch.zeros(8, 1, device="cuda:0")
+    # out sits inside its own sentinel buffer: the 2048 elements behind it
+    # are where a write past the capacity would land
+    back = torch.full((256 + 8 + 2048,), -7.0, device="cuda:0")
+    out = back[256:264].view(8, 1)
+    out.zero_()
     v, off = store.get_csr("clamp", [0, 1, 2, 3], out=out)
     torch.cuda.synchronize()
     q = store.query("clamp")
     assert q["cap_skipped"] == 2, q
     assert torch.equal(out.cpu(), vals[:8])
     assert (guard == -7.0).all()  # nothing wrote past the capacity buffer
+    assert (back[:256] == -7.0).all() and (back[264:] == -7.0).all()
     assert q["bytes_gathered"] == 8 * 4  # true bytes, not 4-sample total
 
 
