@@ -7,9 +7,9 @@ RCCL (torch.distributed "nccl") metadata plane, POSIX-shm CPU compatibility
 path. See ddstore_amd/csrc for the native core.
 """
 from .comm import Comm, as_comm
-from .store import DDStore
+from .store import DDStore, GraphBatch
 from .distdataset import DistDataset, nsplit
-from .prefetch import PrefetchLoader
+from .prefetch import GraphPrefetchLoader, PrefetchLoader
 from .reshuffle import reshuffle_epoch
 from . import debug, io
 
@@ -19,9 +19,11 @@ __all__ = [
     "Comm",
     "as_comm",
     "DDStore",
+    "GraphBatch",
     "DistDataset",
     "nsplit",
     "PrefetchLoader",
+    "GraphPrefetchLoader",
     "reshuffle_epoch",
     "debug",
     "io",

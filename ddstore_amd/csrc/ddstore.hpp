@@ -32,6 +32,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "ddstore_kernels.h"
@@ -670,6 +671,91 @@ public:
         TORCH_CHECK(v.is_csr, "ddstore gather_csr: not a CSR variable");
         check_peers(v);
         check_idx(idx);
+        return csr_fast(v, idx, out);
+    }
+
+    // Graph-batch fetch in one native call: the node variable exactly as
+    // gather_csr_fast fetches it, then the edge-index variable's offsets
+    // (csr_offsets), its edges relabelled to the packed batch
+    // (gather_csr_relabel) and the batch vector plus both tails
+    // (graph_fill); all on stream(), no host reads of device data. x_out's
+    // capacity in elements is Ncap and batch_out holds exactly Ncap int64;
+    // edge_out holds 2 * Ecap ids of the output dtype. Returns (ptr,
+    // edge_ptr), both [n+1] and unclamped. Every element of batch_out and
+    // edge_out is written.
+    std::tuple<at::Tensor, at::Tensor> gather_graph(
+        const std::string& node_name, const std::string& edge_name,
+        const at::Tensor& idx, at::Tensor x_out, at::Tensor edge_out,
+        at::Tensor batch_out, bool coo, int64_t edge_fill) {
+        RoctxRange rr_("ddstore::gather_graph");
+        DeviceVar& nv = var(node_name);
+        DeviceVar& ev = var(edge_name);
+        TORCH_CHECK(nv.is_csr && ev.is_csr, "ddstore gather_graph: not a CSR variable");
+        check_peers(nv);
+        check_peers(ev);
+        check_idx(idx);
+        TORCH_CHECK(ev.row_elems == 2 && (ev.dds_t == DDS_I32 || ev.dds_t == DDS_I64),
+                    "ddstore gather_graph: the edge index must be an int32/int64 "
+                    "variable with disp == 2");
+        TORCH_CHECK(nv.prefix == ev.prefix,
+                    "ddstore gather_graph: node and edge variables are sharded "
+                    "differently");
+        const int64_t nidx = idx.numel();
+        const int64_t ncap = x_out.numel() / std::max<int64_t>(nv.row_elems, 1);
+        TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
+                        batch_out.device().is_cuda() &&
+                        batch_out.device().index() == device_ &&
+                        batch_out.numel() == ncap,
+                    "ddstore gather_graph: batch_out must be a contiguous int64 "
+                    "tensor of x_out's capacity on the store device");
+        TORCH_CHECK(edge_out.is_contiguous() && edge_out.device().is_cuda() &&
+                        edge_out.device().index() == device_ &&
+                        edge_out.numel() % 2 == 0 &&
+                        (edge_out.scalar_type() == at::kLong ||
+                         (edge_out.scalar_type() == at::kInt && ev.dds_t == DDS_I32)),
+                    "ddstore gather_graph: edge_out must be a contiguous int64 "
+                    "tensor (int32 for an int32 variable) of 2 * Ecap elements "
+                    "on the store device");
+        const int out_t = dds_type_of(edge_out);
+        TORCH_CHECK((uintptr_t)edge_out.data_ptr() % dds_itemsize(out_t) == 0 &&
+                        (uintptr_t)batch_out.data_ptr() % 8 == 0,
+                    "ddstore gather_graph: misaligned output");
+        const int64_t ecap = edge_out.numel() / 2;
+        TORCH_CHECK(out_t == DDS_I64 || ncap < (int64_t(1) << 31),
+                    "ddstore gather_graph: int32 node ids need Ncap < 2^31");
+        at::Tensor ptr = csr_fast(nv, idx, x_out);
+        auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
+        at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
+        if (nidx == 0) {
+            edge_ptr.zero_();
+        } else {
+            auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
+            at::Tensor scratch = at::empty(
+                {(int64_t)ddstore::csr_plan_scratch_bytes(nidx)}, bopts);
+            ddstore::csr_offsets(stream(), ev.d_goff, ev.prefix[nparts_],
+                                 idx.data_ptr<int64_t>(), nidx,
+                                 edge_ptr.data_ptr<int64_t>(), scratch.data_ptr(),
+                                 ev.d_oob);
+            ddstore::gather_csr_relabel(
+                stream(), (const void* const*)ev.d_peers, ev.d_prefix,
+                ev.d_elem_prefix, nparts_, ev.d_goff, idx.data_ptr<int64_t>(), nidx,
+                ptr.data_ptr<int64_t>(), edge_ptr.data_ptr<int64_t>(), ncap, ecap,
+                ev.dds_t, out_t, coo, edge_out.data_ptr(), ev.d_oob);
+            ev.n_gather += 1;
+            ev.rows_gathered += nidx;
+            // bytes accounted via the device DDS_CTR_ELEMS counter (see query)
+        }
+        ddstore::graph_fill(stream(), ptr.data_ptr<int64_t>(),
+                            edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, out_t,
+                            coo, edge_fill, batch_out.data_ptr<int64_t>(),
+                            edge_out.data_ptr());
+        return {ptr, edge_ptr};
+    }
+
+private:
+    // body of gather_csr_fast, shared with gather_graph; `v` and `idx` are
+    // checked by the caller
+    at::Tensor csr_fast(DeviceVar& v, const at::Tensor& idx, at::Tensor out) {
         const int64_t nidx = idx.numel();
         TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
                         dds_type_of(out) == v.dds_t,
@@ -702,6 +788,7 @@ public:
         return off;
     }
 
+public:
     // Padded CSR fetch: one launch writes the dense (n, max_len, disp)
     // batch (cast / affine fused, pad broadcast from `pad_bits`, the raw
     // bits of one output element) and the true per-sample lengths. The

@@ -55,6 +55,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("gather_csr", &DeviceStore::gather_csr, py::call_guard<py::gil_scoped_release>())
         .def("csr_lens", &DeviceStore::csr_lens, py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_fast", &DeviceStore::gather_csr_fast, py::call_guard<py::gil_scoped_release>())
+        .def("gather_graph", &DeviceStore::gather_graph, py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_padded", &DeviceStore::gather_csr_padded,
              py::arg("name"), py::arg("idx"), py::arg("out"), py::arg("lengths"),
              py::arg("max_len"), py::arg("pad_bits"), py::arg("affine") = false,

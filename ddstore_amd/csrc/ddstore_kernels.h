@@ -166,6 +166,44 @@ void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
                        void* d_out, int64_t* d_lengths,
                        unsigned long long* d_ctrs);
 
+// Graph-batch fetch (DeviceStore::gather_graph): the pieces beside the node
+// features, which gather_csr_balanced fetches unchanged.
+//
+// csr_offsets: d_out_off[0..nidx] = exclusive scan of the requested samples'
+// lengths (a bad index has length 0), never clamped. It runs k_csr_plan1 and
+// k_csr_plan2 as they are, so bad indices count in d_ctrs[DDS_CTR_OOB] and the
+// requested total is ADDED to d_ctrs[DDS_CTR_ELEMS]: the gather that follows
+// takes back what it drops. d_scratch: csr_plan_scratch_bytes(nidx) bytes.
+void csr_offsets(hipStream_t stream, const int64_t* d_goff, int64_t nsamples_total,
+                 const int64_t* d_idx, int64_t nidx, int64_t* d_out_off,
+                 void* d_scratch, unsigned long long* d_ctrs);
+
+// Relabelling gather of an edge-index variable (2 ids per element, in_t
+// DDS_I32 or DDS_I64; out_t DDS_I64, or DDS_I32 for DDS_I32 input). d_ptr and
+// d_edge_ptr are the [nidx+1] node and edge offsets of the request. The edges
+// of graph s are written iff d_ptr[s+1] <= ncap and d_edge_ptr[s+1] <= ecap:
+// id + d_ptr[s], edge e at column d_edge_ptr[s] + e of a (2, ecap) output
+// (coo) or at that row of an (ecap, 2) output. A graph with edges that are
+// not written counts once in d_ctrs[DDS_CTR_CAP] and its edges are subtracted
+// from d_ctrs[DDS_CTR_ELEMS]. Slots of no kept edge are left to graph_fill.
+void gather_csr_relabel(hipStream_t stream, const void* const* d_peer_base,
+                        const int64_t* d_sample_prefix,
+                        const int64_t* d_elem_prefix, int nparts,
+                        const int64_t* d_goff, const int64_t* d_idx, int64_t nidx,
+                        const int64_t* d_ptr, const int64_t* d_edge_ptr,
+                        int64_t ncap, int64_t ecap, int in_t, int out_t, bool coo,
+                        void* d_out, unsigned long long* d_ctrs);
+
+// The rest of a graph batch, one launch, no atomics: d_batch[j] = s for the
+// nodes of every graph with d_ptr[s+1] <= ncap and nidx for the slots behind
+// them up to ncap; every edge_index slot behind the kept edges (the graphs
+// gather_csr_relabel writes) up to ecap = edge_fill. Together with
+// gather_csr_relabel every element of both buffers is written exactly once.
+// d_ptr / d_edge_ptr must hold nidx + 1 entries (one zero for nidx == 0).
+void graph_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_ptr,
+                int64_t nidx, int64_t ncap, int64_t ecap, int out_t, bool coo,
+                int64_t edge_fill, int64_t* d_batch, void* d_edge_out);
+
 // Scatter rows of a packed buffer into the local shard at arbitrary local row
 // ids (inverse of gather_rows with nparts==1). Used by the epoch reshuffle to
 // place all-to-all-received rows.

@@ -221,3 +221,81 @@ class PrefetchLoader:
             nxt = i + self.depth
             if nxt < nb:
                 launch(nxt)
+
+
+class GraphPrefetchLoader(PrefetchLoader):
+    """Iterate minibatches of whole graphs, fetched with
+    :meth:`DDStore.get_graph_batch` on the side streams; yields
+    :class:`~ddstore_amd.store.GraphBatch`, or ``(GraphBatch, label)`` with
+    ``label_name``.
+
+    The ``x``, ``edge_index`` and ``batch`` buffers live in the ring slots and
+    are sized for the worst batch from the host copy of the offsets
+    (``batch_size * max nodes`` and ``batch_size * max edges``), so a fetch
+    never syncs and never drops a graph; the slack holds the dummy segment
+    (``batch == n``) and ``edge_fill``. A yielded batch's buffers are reused
+    ``depth`` batches later, as in :class:`PrefetchLoader`.
+
+    Parameters
+    ----------
+    store : DDStore
+    node_name : str         node-aligned CSR variable (features)
+    edge_index_name : str   edge-aligned CSR variable, ``disp == 2``
+    indices, batch_size, label_name, depth, drop_last : as PrefetchLoader
+    coo, edge_dtype, edge_fill : as get_graph_batch
+    """
+
+    def __init__(
+        self,
+        store: DDStore,
+        node_name: str,
+        edge_index_name: str,
+        indices: Union[Sequence[int], torch.Tensor, np.ndarray],
+        batch_size: int,
+        label_name: Optional[str] = None,
+        depth: Optional[int] = None,
+        drop_last: bool = False,
+        coo: bool = True,
+        edge_dtype: Optional[torch.dtype] = None,
+        edge_fill: int = -1,
+    ):
+        # refuses a bad pair of variables here, not at the first batch
+        _, emeta, self._edge_out_dtype = store._graph_pair(
+            node_name, edge_index_name, edge_dtype)
+        super().__init__(store, node_name, indices, batch_size,
+                         label_name=label_name, depth=depth, drop_last=drop_last)
+        self.edge_index_name = edge_index_name
+        self.coo = bool(coo)
+        self.edge_dtype = edge_dtype
+        self.edge_fill = edge_fill
+        goff = emeta["goff"]
+        self._max_edges = int((goff[1:] - goff[:-1]).max().item()) if goff.numel() > 1 else 0
+
+    def _fetch(self, b: torch.Tensor, slot: Optional[dict] = None):
+        store = self.store
+        meta = store._meta(self.name)
+        ncap = b.numel() * self._max_len
+        ecap = b.numel() * self._max_edges
+        bufs = None if slot is None else slot.get("data")
+        if bufs is None or bufs[2].numel() != ncap or bufs[1].numel() != 2 * ecap:
+            # first use of the slot, or a ragged final batch
+            bufs = (
+                torch.empty((ncap, meta["disp"]), dtype=meta["dtype"], device=store.device),
+                torch.empty(2 * ecap, dtype=self._edge_out_dtype, device=store.device),
+                torch.empty(ncap, dtype=torch.int64, device=store.device),
+            )
+        data = store.get_graph_batch(
+            self.name, self.edge_index_name, b, x_out=bufs[0], edge_out=bufs[1],
+            batch_out=bufs[2], coo=self.coo, edge_dtype=self.edge_dtype,
+            edge_fill=self.edge_fill)
+        if slot is not None:
+            slot["data"] = bufs
+        if self.label_name is None:
+            return data, None
+        lbuf = None if slot is None else slot.get("label")
+        if lbuf is not None and lbuf.shape[0] != b.numel():
+            lbuf = None
+        label = store.get_batch(self.label_name, b, out=lbuf, dtype=self.label_dtype)
+        if slot is not None:
+            slot["label"] = label
+        return data, label

@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import os
 import uuid
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -50,6 +50,19 @@ _SUPPORTED = {
     torch.float8_e4m3fn,
     torch.float8_e5m2,
 }
+
+
+class GraphBatch(NamedTuple):
+    """One packed minibatch of graphs, as :meth:`DDStore.get_graph_batch`
+    returns it (``n`` requested graphs, buffer capacities ``Ncap``/``Ecap``)."""
+
+    x: torch.Tensor            # (Ncap, disp) packed node features
+    edge_index: torch.Tensor   # (2, Ecap), or (Ecap, 2) with coo=False
+    ptr: torch.Tensor          # int64 (n+1,) node offsets
+    edge_ptr: torch.Tensor     # int64 (n+1,) edge offsets
+    batch: torch.Tensor        # int64 (Ncap,) graph id of every node
+    node_extras: tuple         # ((values, offsets), ...)
+    edge_extras: tuple
 
 
 def _as_tensor(arr: ArrayLike) -> torch.Tensor:
@@ -141,6 +154,10 @@ class DDStore:
             group_id = self.world_comm.rank - self.rank
             self._backend = _C.HostStore(f"{session}g{group_id}", self.rank, self.size)
         self._vars: Dict[str, dict] = {}
+        # get_graph_batch: validated (node, edge index) pairs and the cached
+        # verdicts on extras, by (extra, anchor) names
+        self._graph_pairs: set = set()
+        self._graph_extras_ok: Dict[tuple, bool] = {}
         self._freed = False
         # per-peer traffic accounting (local vs each remote rank), enabled via
         # DDSTORE_STATS=1 -- the reference has no observability at all
@@ -525,6 +542,228 @@ class DDStore:
             return dense_v.contiguous(), lengths
         out.view(n, max_len, disp).copy_(dense_v)
         return out.view(n, max_len, disp), lengths
+
+    # ----------------------------------------------------------- graph batches
+    def _graph_pair(self, node_name: str, edge_index_name: str, edge_dtype):
+        """Host-side validation of a (node, edge index) pair, done once per
+        pair of names; returns ``(node meta, edge meta, output dtype)``."""
+        nmeta, emeta = self._meta(node_name), self._meta(edge_index_name)
+        if (node_name, edge_index_name) not in self._graph_pairs:
+            for nm, m in ((node_name, nmeta), (edge_index_name, emeta)):
+                if not m["is_csr"]:
+                    raise ValueError(
+                        f"ddstore get_graph_batch: '{nm}' is not a CSR variable")
+            if emeta["disp"] != 2:
+                raise ValueError(
+                    f"ddstore get_graph_batch: edge index '{edge_index_name}' "
+                    f"must have disp == 2 (rows of (src, dst)), has {emeta['disp']}")
+            if emeta["dtype"] not in (torch.int32, torch.int64):
+                raise TypeError(
+                    f"ddstore get_graph_batch: edge index '{edge_index_name}' "
+                    f"must be int32 or int64, is {emeta['dtype']}")
+            pn = list(self._backend.query(node_name)["prefix"])
+            pe = list(self._backend.query(edge_index_name)["prefix"])
+            if pn != pe:
+                raise ValueError(
+                    "ddstore get_graph_batch: node and edge variables hold "
+                    "different numbers of samples per rank")
+            self._graph_pairs.add((node_name, edge_index_name))
+        out_dtype = edge_dtype or torch.int64
+        if out_dtype not in (torch.int32, torch.int64):
+            raise TypeError("ddstore get_graph_batch: edge_dtype must be int32 or int64")
+        if out_dtype == torch.int32 and emeta["dtype"] != torch.int32:
+            raise TypeError(
+                "ddstore get_graph_batch: an int64 edge index is not narrowed to int32")
+        return nmeta, emeta, out_dtype
+
+    def _graph_extra(self, name: str, anchor: str) -> None:
+        """An extra must be cut into samples exactly as its anchor variable
+        (same global offsets); checked once per pair of names."""
+        key = (name, anchor)
+        if key not in self._graph_extras_ok:
+            meta = self._meta(name)
+            if not meta["is_csr"]:
+                raise ValueError(f"ddstore get_graph_batch: '{name}' is not a CSR variable")
+            self._graph_extras_ok[key] = torch.equal(meta["goff"],
+                                                     self._meta(anchor)["goff"])
+        if not self._graph_extras_ok[key]:
+            raise ValueError(
+                f"ddstore get_graph_batch: '{name}' does not have the sample "
+                f"lengths of '{anchor}'")
+
+    def get_graph_batch(
+        self,
+        node_name: str,
+        edge_index_name: str,
+        indices: ArrayLike,
+        *,
+        x_out: Optional[torch.Tensor] = None,
+        edge_out: Optional[torch.Tensor] = None,
+        batch_out: Optional[torch.Tensor] = None,
+        coo: bool = True,
+        edge_dtype: Optional[torch.dtype] = None,
+        edge_fill: int = -1,
+        node_extras: Sequence[str] = (),
+        edge_extras: Sequence[str] = (),
+    ) -> GraphBatch:
+        """Fetch a minibatch of whole graphs for a message-passing model:
+        packed node features, the edge index relabelled to the packed batch,
+        and the batch vector. On the GPU this is one native call with no host
+        sync when the three buffers are passed.
+
+        Storage convention: graphs are the samples of two groups of CSR
+        variables. Node-aligned variables (``node_name``, ``node_extras``)
+        have ``lengths[i]`` = nodes of graph ``i``; edge-aligned ones
+        (``edge_index_name``, ``edge_extras``) have ``lengths[i]`` = edges of
+        graph ``i``. The edge index has ``disp == 2``, dtype int64 or int32:
+        row ``e`` of graph ``i`` is ``(src, dst)`` with node ids LOCAL to the
+        graph, in ``[0, nodes_i)`` (a ``(2, E)`` array is transposed once
+        before :meth:`add_csr`). Stored ids are not validated: an id outside
+        its graph gives an edge that names some other node or none.
+
+        With ``n = len(indices)`` the result holds
+
+        * ``x`` ``(Ncap, disp)``: exactly ``get_csr(node_name, indices,
+          out=x_out)[0]``; ``ptr`` int64 ``(n+1,)`` its offsets;
+        * ``edge_ptr`` int64 ``(n+1,)``: the edge offsets, never clamped;
+        * ``edge_index`` ``(2, Ecap)`` (``(Ecap, 2)`` with ``coo=False``) of
+          ``edge_dtype`` (default int64; int32 only for an int32 variable):
+          edge ``e`` of graph ``i`` is ``stored_id + ptr[i]`` at column (row)
+          ``edge_ptr[i] + e``;
+        * ``batch`` int64 ``(Ncap,)``: ``batch[j] = i`` for ``ptr[i] <= j <
+          ptr[i+1]``.
+
+        ``Ncap``/``Ecap`` are the capacities of the caller's buffers: ``x_out``
+        as for :meth:`get_csr`, ``batch_out`` int64 with exactly ``Ncap``
+        elements, ``edge_out`` contiguous of the output dtype with exactly
+        ``2 * Ecap`` elements. Pass all three or none; without them they are
+        sized exactly from the host copy of the offsets (which costs a sync if
+        ``indices`` lives on the device).
+
+        Undersized buffers: graphs are kept as a prefix of the request. A
+        graph's nodes are kept as :meth:`get_csr` decides (its slice ends at
+        or before ``Ncap``); its edges are written only if its nodes were kept
+        and its edge slice ends at or before ``Ecap``, so a written edge never
+        names a node that was not written. A graph whose nodes fit but whose
+        edges do not keeps its nodes, which then appear as isolated nodes; the
+        caller sees it as ``edge_ptr[-1] > Ecap``, and each such graph with at
+        least one edge counts once in the edge variable's ``cap_skipped``.
+
+        Every element of ``batch`` and ``edge_index`` is written (no pre-fill
+        needed): ``batch[j] = n`` for slots of no kept node -- a dummy segment,
+        so a consumer can reduce into ``n + 1`` segments without a mask -- and
+        ``edge_fill`` (converted once to the output dtype, never shifted) in
+        every slot of no kept edge. The slack of ``x`` stays untouched. A bad
+        index has length 0 in ``ptr`` and ``edge_ptr`` and counts once in
+        ``oob_skipped`` of both variables.
+
+        ``node_extras``/``edge_extras`` name further CSR variables with the
+        same sample lengths as the node / edge-index variable; each is fetched
+        with :meth:`get_csr` and the same indices and comes back as
+        ``(values, offsets)``."""
+        nmeta, emeta, out_dtype = self._graph_pair(node_name, edge_index_name,
+                                                   edge_dtype)
+        for nm in node_extras:
+            self._graph_extra(nm, node_name)
+        for nm in edge_extras:
+            self._graph_extra(nm, edge_index_name)
+        bufs = (x_out, edge_out, batch_out)
+        if any(b is None for b in bufs) and not all(b is None for b in bufs):
+            raise ValueError(
+                "ddstore get_graph_batch: pass x_out, edge_out and batch_out together")
+        idx = torch.as_tensor(indices, dtype=torch.int64).flatten()
+        n, disp = idx.numel(), nmeta["disp"]
+        fill = int(torch.tensor([edge_fill], dtype=out_dtype).item())
+        if x_out is None:
+            # exact sizes from the host offsets (a device `indices` syncs here)
+            ih = idx.cpu()
+            ih = ih[(ih >= 0) & (ih < nmeta["nrows_total"])]
+            gn, ge = nmeta["goff"], emeta["goff"]
+            ncap = int((gn[ih + 1] - gn[ih]).sum())
+            ecap = int((ge[ih + 1] - ge[ih]).sum())
+            x_out = torch.empty((ncap, disp), dtype=nmeta["dtype"], device=self.device)
+            edge_out = torch.empty(2 * ecap, dtype=out_dtype, device=self.device)
+            batch_out = torch.empty(ncap, dtype=torch.int64, device=self.device)
+        else:
+            ncap = x_out.numel() // max(disp, 1)
+            if (batch_out.dtype != torch.int64 or not batch_out.is_contiguous()
+                    or batch_out.device != self.device or batch_out.numel() != ncap):
+                raise ValueError(
+                    "ddstore get_graph_batch: batch_out must be a contiguous "
+                    f"int64 tensor of {ncap} elements (x_out's capacity) on the "
+                    "store device")
+            if (edge_out.dtype != out_dtype or not edge_out.is_contiguous()
+                    or edge_out.device != self.device or edge_out.numel() % 2):
+                raise ValueError(
+                    "ddstore get_graph_batch: edge_out must be a contiguous "
+                    f"{out_dtype} tensor of 2 * Ecap elements on the store device")
+            ecap = edge_out.numel() // 2
+        if out_dtype == torch.int32 and ncap >= 2 ** 31:
+            raise ValueError("ddstore get_graph_batch: int32 node ids need Ncap < 2**31")
+        idx = idx.to(self.device, non_blocking=True).contiguous()
+        if self.mode == "hip":
+            self._account(nmeta, idx)
+            self._account(emeta, idx)
+            ptr, edge_ptr = self._backend.gather_graph(
+                node_name, edge_index_name, idx, x_out, edge_out, batch_out,
+                bool(coo), fill)
+            x = x_out
+        else:
+            x, ptr, edge_ptr = self._graph_batch_host(
+                node_name, edge_index_name, idx, x_out, edge_out, batch_out,
+                ncap, ecap, bool(coo), fill)
+        edge_index = edge_out.view(2, ecap) if coo else edge_out.view(ecap, 2)
+        return GraphBatch(
+            x, edge_index, ptr, edge_ptr, batch_out.view(ncap),
+            tuple(self.get_csr(nm, idx) for nm in node_extras),
+            tuple(self.get_csr(nm, idx) for nm in edge_extras))
+
+    def _graph_batch_host(self, node_name, edge_index_name, idx, x_out, edge_out,
+                          batch_out, ncap, ecap, coo, fill):
+        """Host path of :meth:`get_graph_batch`: the existing CSR gather plus
+        torch ops, same semantics as the kernels."""
+        nmeta, emeta = self._meta(node_name), self._meta(edge_index_name)
+        n = idx.numel()
+        ok = (idx >= 0) & (idx < emeta["nrows_total"])
+        safe = torch.where(ok, idx, torch.zeros_like(idx))
+
+        def offsets(goff):  # a bad index has length 0
+            lens = torch.where(ok, goff[safe + 1] - goff[safe], torch.zeros_like(idx))
+            off = torch.zeros(n + 1, dtype=torch.int64)
+            torch.cumsum(lens, 0, out=off[1:])
+            return lens, off
+
+        _, ptr = offsets(nmeta["goff"])
+        elen, edge_ptr = offsets(emeta["goff"])
+        # nodes: what get_csr(out=) does on this path (its gather skips and
+        # counts bad indices and graphs that end past the capacity)
+        self._account(nmeta, idx)
+        self._backend.gather_csr(node_name, idx, ptr, x_out, ncap)
+        x = x_out
+        # both offset arrays are monotone: the kept graphs are prefixes
+        nodes_fit = ptr[1:] <= ncap
+        kn = int(nodes_fit.sum())
+        ke = int((nodes_fit & (edge_ptr[1:] <= ecap)).sum())
+        node_end, edge_end = int(ptr[kn]), int(edge_ptr[ke])
+        batch = batch_out.view(ncap)
+        batch[node_end:] = n
+        batch[:node_end] = torch.repeat_interleave(
+            torch.arange(kn, dtype=torch.int64), ptr[1:kn + 1] - ptr[:kn])
+        # a buffer of exactly the kept edges: the gather skips and counts the
+        # graphs behind it, as the relabelling kernel does
+        stored = torch.empty((edge_end, 2), dtype=emeta["dtype"])
+        self._backend.gather_csr(edge_index_name, idx, edge_ptr, stored, edge_end)
+        shift = torch.repeat_interleave(ptr[:ke], elen[:ke]).unsqueeze(1)
+        kept = (stored.to(torch.int64) + shift).to(edge_out.dtype)
+        if coo:
+            ev = edge_out.view(2, ecap)
+            ev[:, edge_end:] = fill
+            ev[:, :edge_end] = kept.t()
+        else:
+            ev = edge_out.view(ecap, 2)
+            ev[edge_end:] = fill
+            ev[:edge_end] = kept
+        return x, ptr, edge_ptr
 
     def local_shard(self, name: str) -> torch.Tensor:
         """Zero-copy view of this rank's shard (rows x disp). Valid until

@@ -7,10 +7,14 @@ README.md:200-212). This example shows that loop MI355X-native: each rank
 owns a shard of variable-length graphs (node-feature matrices) in HBM, every
 epoch draws a DistributedSampler-style global shuffle, minibatches of whole
 graphs are packed by the CSR gather kernel (remote graphs over xGMI), pooled
-per-graph, and pushed through a bf16 classifier with DDP.
+per-graph, and pushed through a bf16 classifier with DDP. With ``--edges``
+every graph also stores an edge index, batches come from the fused
+graph-batch fetch (GraphPrefetchLoader) and one message-passing layer runs
+before the pooling.
 
 Launch:
   python examples/gnn_csr_train.py --epochs 2
+  python examples/gnn_csr_train.py --epochs 2 --edges
   torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 8 \
       examples/gnn_csr_train.py --epochs 2
 """
@@ -24,7 +28,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 
-from ddstore_amd import DDStore, PrefetchLoader  # noqa: E402
+from ddstore_amd import DDStore, GraphPrefetchLoader, PrefetchLoader  # noqa: E402
 
 FEAT = 16
 
@@ -49,8 +53,46 @@ def masked_mean(dense: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
     return (dense.float().sum(1) / n).to(dense.dtype)
 
 
+def synthetic_edges(lens: torch.Tensor, chords: int, g: torch.Generator):
+    """A ring plus ``chords`` random chords per graph, node ids local to the
+    graph: ``(pairs (E, 2) int32, edges per graph)``."""
+    n_edges = lens + chords
+    gid = torch.repeat_interleave(torch.arange(lens.numel()), n_edges)
+    start = torch.cumsum(n_edges, 0) - n_edges
+    k = torch.arange(int(n_edges.sum())) - start[gid]  # edge number in its graph
+    n = lens[gid]
+    ring = k < n
+    rnd = torch.randint(0, 1 << 30, (k.numel(), 2), generator=g)
+    src = torch.where(ring, k, rnd[:, 0] % n)
+    dst = torch.where(ring, (k + 1) % n, rnd[:, 1] % n)
+    return torch.stack([src, dst], 1).to(torch.int32), n_edges
+
+
+def message_pass(gb) -> torch.Tensor:
+    """One neighbour-mean layer then mean pooling, on a GraphBatch whose
+    buffers carry slack: ``edge_index`` slots past the batch's edges hold -1
+    and ``batch`` slots past its nodes hold the dummy segment ``n``."""
+    x, (src, dst) = gb.x, gb.edge_index.long()
+    live = (src >= 0).unsqueeze(1).to(x.dtype)
+    src, dst = src.clamp(min=0), dst.clamp(min=0)
+    agg = torch.zeros_like(x).index_add_(0, dst, x[src] * live)
+    deg = torch.zeros(x.shape[0], 1, device=x.device, dtype=x.dtype).index_add_(0, dst, live)
+    h = 0.5 * (x + agg / deg.clamp(min=1))
+    n = gb.ptr.numel() - 1
+    # slack rows of x are uninitialised: the dummy segment swallows them
+    pooled = torch.zeros(n + 1, x.shape[1], device=x.device, dtype=x.dtype)
+    pooled.index_add_(0, gb.batch, torch.where(gb.batch.unsqueeze(1) < n, h,
+                                               torch.zeros_like(h)))
+    nodes = (gb.ptr[1:] - gb.ptr[:-1]).clamp(min=1).unsqueeze(1)
+    return pooled[:n] / nodes.to(x.dtype)
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--edges", action="store_true",
+                   help="store an edge index per graph, fetch whole graph "
+                        "batches with GraphPrefetchLoader and run one "
+                        "message-passing layer before the pooling")
     p.add_argument("--epochs", type=int, default=2)
     p.add_argument("--padded", action="store_true",
                    help="fetch fixed-shape (B, L, FEAT) bf16 batches with the "
@@ -90,6 +132,9 @@ def main():
     feats = centers.unsqueeze(1) + 0.1 * torch.randn(total_nodes, FEAT, generator=g)
     store.add_csr("graphs", feats, lens)
     store.add("labels", labels_local.unsqueeze(1))
+    if args.edges:
+        pairs, n_edges = synthetic_edges(lens, 3, g)
+        store.add_csr("edge_index", pairs, n_edges)
 
     model = nn.Sequential(
         nn.Linear(FEAT, 128), nn.GELU(), nn.Linear(128, 4)
@@ -108,7 +153,11 @@ def main():
         store.epoch_begin()
         # CSR prefetch: next batch's variable-length gather runs on a side
         # HIP stream while this batch trains
-        if args.padded:
+        if args.edges:
+            loader = GraphPrefetchLoader(store, "graphs", "edge_index", mine,
+                                         args.batch_size, label_name="labels",
+                                         drop_last=True, edge_dtype=torch.int32)
+        elif args.padded:
             # graphs have at most 59 nodes: nothing is truncated at 60
             loader = PrefetchLoader(store, "graphs", mine, args.batch_size,
                                     label_name="labels", drop_last=True,
@@ -116,9 +165,12 @@ def main():
         else:
             loader = PrefetchLoader(store, "graphs", mine, args.batch_size,
                                     label_name="labels", drop_last=True)
-        for (values, offsets), y in loader:
+        for data, y in loader:
             y = y.view(-1).long()
-            if args.padded:  # (dense, lengths): bf16 straight from the gather
+            values, offsets = (None, None) if args.edges else data
+            if args.edges:  # no host sync: shapes come from the buffers
+                x = message_pass(data).to(torch.bfloat16)
+            elif args.padded:  # (dense, lengths): bf16 straight from the gather
                 x = masked_mean(values, offsets)
             else:
                 x = segment_mean(values[: int(offsets[-1])], offsets).to(torch.bfloat16)
