@@ -94,10 +94,34 @@ template <typename T>
 constexpr bool is_fp8_v =
     std::is_same_v<T, __hip_fp8_e4m3> || std::is_same_v<T, __hip_fp8_e5m2>;
 
+// f64 -> f32 as a rounding of its own. HIP compiles with -ffp-contract=fast,
+// which flags every conversion `contract`; the backend then merges
+// (f16)(float)x into ONE f64 -> f16 rounding (and the same for bf16), while
+// the contract (docs/API.md, cast semantics) and the host backend round
+// twice. With contraction off for this one conversion the merge does not
+// happen.
+__device__ __forceinline__ float f64_to_f32(double v) {
+#pragma clang fp contract(off)
+    return static_cast<float>(v);
+}
+
 template <typename Tout, typename Tin>
 __device__ __forceinline__ Tout cvt(Tin v) {
     if constexpr (std::is_same_v<Tout, Tin>) {
         return v;
+    } else if constexpr (std::is_same_v<Tin, double> &&
+                         (std::is_same_v<Tout, __half> ||
+                          std::is_same_v<Tout, __hip_bfloat16>)) {
+        return cvt<Tout, float>(f64_to_f32(v));
+    } else if constexpr (std::is_same_v<Tout, uint8_t> &&
+                         std::is_floating_point_v<Tin>) {
+        // A value outside 0..255 is unspecified by the contract, but it must
+        // stay in its own byte. The plain cast is undefined there, so the
+        // compiler packed the unmasked 32-bit converts of a 16-B chunk with
+        // ORs and -3.0f (0xFFFFFFFD) overwrote its neighbours. Through int32
+        // the narrowing is an integer truncation, which is masked; the low
+        // byte is what the cast gave before, element by element.
+        return static_cast<uint8_t>(static_cast<int32_t>(v));
     } else if constexpr (std::is_same_v<Tin, __half>) {
         return cvt<Tout, float>(__half2float(v));
     } else if constexpr (std::is_same_v<Tin, __hip_bfloat16>) {
@@ -109,7 +133,19 @@ __device__ __forceinline__ Tout cvt(Tin v) {
     } else if constexpr (std::is_same_v<Tout, __hip_bfloat16>) {
         return __float2bfloat16(static_cast<float>(v));
     } else if constexpr (is_fp8_v<Tout>) {
-        return Tout(static_cast<float>(v));
+        // The fp8 constructors saturate to the largest finite value; the
+        // contract (docs/API.md, cast semantics) is torch's: past the
+        // midpoint above the largest finite value, ties to even deciding the
+        // midpoint itself, e4m3fn gives NaN (also for +-inf) and e5m2 +-inf.
+        // A NaN fails both compares and converts as before.
+        const float f = static_cast<float>(v);
+        Tout r(f);
+        if constexpr (std::is_same_v<Tout, __hip_fp8_e4m3>) {
+            if (fabsf(f) > 464.0f) r.__x = 0x7F;
+        } else {
+            if (fabsf(f) >= 61440.0f) r.__x = f < 0.0f ? 0xFC : 0x7C;
+        }
+        return r;
     } else {
         return static_cast<Tout>(v);
     }
@@ -131,9 +167,18 @@ struct XfCast {
 };
 struct XfAffine {
     float scale, shift;
+    // Always 0, but only the host knows. For an f16 output the compiler
+    // selects v_fma_mixlo_f16 for fmaf + convert, which rounds the exact sum
+    // ONCE, to f16, while the contract is the fma rounded to f32 and that
+    // value cast. OR-ing the f32 result with this kernel argument keeps the
+    // two roundings apart (one v_or_b32 per element, f16 outputs only).
+    uint32_t opaque_zero = 0;
     template <typename Tout, typename Tin>
     __device__ __forceinline__ Tout apply(Tin v) const {
-        return cvt<Tout>(fmaf(cvt<float>(v), scale, shift));
+        float y = fmaf(cvt<float>(v), scale, shift);
+        if constexpr (std::is_same_v<Tout, __half>)
+            y = __uint_as_float(__float_as_uint(y) | opaque_zero);
+        return cvt<Tout>(y);
     }
 };
 

@@ -340,6 +340,16 @@ class DDStore:
         self._backend.update_elems(name, self._staged(v), elem_off)
 
     # ------------------------------------------------------------------- reads
+    def _check_out_dtype(self, what: str, name: str, out_dtype) -> None:
+        """The store has no bool element kind (bool is stored and moved as
+        bytes 0/1), so it cannot CONVERT to bool: a bool output is a byte move
+        of a variable stored as bool and refused for every other variable."""
+        if out_dtype == torch.bool and self._meta(name)["dtype"] != torch.bool:
+            raise TypeError(
+                f"ddstore {what}: bool output needs a variable stored as bool "
+                f"('{name}' holds {self._vars[name]['dtype']}); fetch it as is "
+                "and compare with 0")
+
     def get(self, name: str, out: ArrayLike, start: int = 0) -> None:
         """Reference-compatible dense read: fills ``out`` with rows
         ``[start, start+len(out))``; the range may not cross a shard boundary
@@ -378,6 +388,8 @@ class DDStore:
         idx = torch.as_tensor(indices, dtype=torch.int64)
         idx = idx.to(self.device, non_blocking=True).contiguous()
         n = idx.numel()
+        self._check_out_dtype("get_batch", name,
+                              out.dtype if out is not None else dtype)
         if out is None:
             out = torch.empty(
                 (n, meta["disp"]), dtype=dtype or meta["dtype"], device=self.device
@@ -410,6 +422,7 @@ class DDStore:
         contiguous int64 tensor on the store device and ``out`` a matching
         output tensor (as returned/validated by a prior :meth:`get_batch`).
         Skips Python-side normalization; the native layer still validates."""
+        self._check_out_dtype("gather_into", name, out.dtype)
         self._backend.gather(name, idx_dev, out)
 
     def get_csr(
@@ -483,6 +496,7 @@ class DDStore:
         idx = idx.to(self.device, non_blocking=True).contiguous()
         n, disp = idx.numel(), meta["disp"]
         out_dtype = dtype or (out.dtype if out is not None else meta["dtype"])
+        self._check_out_dtype("get_csr_padded", name, out_dtype)
         if out is not None:
             if (not out.is_contiguous() or out.device != self.device
                     or out.dtype != out_dtype or out.numel() != n * max_len * disp):
