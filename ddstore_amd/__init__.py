@@ -7,7 +7,7 @@ RCCL (torch.distributed "nccl") metadata plane, POSIX-shm CPU compatibility
 path. See ddstore_amd/csrc for the native core.
 """
 from .comm import Comm, as_comm
-from .store import DDStore, GraphBatch
+from .store import ColumnStats, DDStore, GraphBatch
 from .distdataset import DistDataset, nsplit
 from .prefetch import GraphPrefetchLoader, PrefetchLoader
 from .reshuffle import reshuffle_epoch
@@ -20,6 +20,7 @@ __all__ = [
     "as_comm",
     "DDStore",
     "GraphBatch",
+    "ColumnStats",
     "DistDataset",
     "nsplit",
     "PrefetchLoader",

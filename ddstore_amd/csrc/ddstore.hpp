@@ -28,6 +28,7 @@
 #include <cstring>
 #include <exception>
 #include <functional>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <string>
@@ -628,6 +629,71 @@ public:
         v.bytes_gathered += nidx * v.row_elems * v.itemsize;
     }
 
+    // One per-column affine vector: `n` contiguous floats on the store
+    // device, 16-B aligned (the kernels load them as vectors).
+    const float* affine_vec(const at::Tensor& t, int64_t n) const {
+        TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                        t.device().is_cuda() && t.device().index() == device_ &&
+                        t.numel() == n,
+                    "ddstore: a per-column affine vector must be a contiguous float32 "
+                    "tensor of disp = ", n, " values on the store device");
+        TORCH_CHECK(((uintptr_t)t.data_ptr()) % 16 == 0,
+                    "ddstore: a per-column affine vector must be 16-byte aligned");
+        return t.data_ptr<float>();
+    }
+
+    // gather_affine with one (scale, shift) pair per column.
+    void gather_affine_cols(const std::string& name, const at::Tensor& idx,
+                            at::Tensor out, const at::Tensor& scale,
+                            const at::Tensor& shift) {
+        RoctxRange rr_("ddstore::gather_affine_cols");
+        DeviceVar& v = var(name);
+        TORCH_CHECK(!v.is_csr, "ddstore gather: use gather_csr for CSR variables");
+        check_peers(v);
+        check_idx(idx);
+        int64_t nidx = idx.numel();
+        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
+                        out.device().index() == device_,
+                    "ddstore gather: output must be a contiguous tensor on the store device");
+        TORCH_CHECK(out.numel() == nidx * v.row_elems, "ddstore gather: shape mismatch");
+        int out_t = dds_type_of(out);
+        TORCH_CHECK(out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
+                    "ddstore gather: affine output must be f32/f16/bf16");
+        TORCH_CHECK(v.row_elems < (int64_t(1) << 31), "ddstore gather: row too long");
+        ddstore::gather_rows_affine_cols(
+            stream(), (const void* const*)v.d_peers, v.d_prefix,
+            (const void* const*)v.peers.data(), v.prefix.data(), nparts_,
+            idx.data_ptr<int64_t>(), nidx, v.row_elems, v.dds_t, out_t,
+            affine_vec(scale, v.row_elems), affine_vec(shift, v.row_elems),
+            out.data_ptr(), v.d_oob);
+        v.n_gather += 1;
+        v.rows_gathered += nidx;
+        v.bytes_gathered += nidx * v.row_elems * v.itemsize;
+    }
+
+    // Column statistics of the local shard (fixed-stride: rows; CSR:
+    // elements): a CPU f64 tensor (5, disp) = pivot, offset (mean = pivot +
+    // offset), M2, min, max, as ddstore::column_stats writes it. Two kernels
+    // on stream(), read back with one sync; scratch is
+    // colstats_scratch_bytes, independent of the number of rows. Reads the
+    // local shard only and touches no gather counter.
+    at::Tensor column_stats(const std::string& name) {
+        RoctxRange rr_("ddstore::column_stats");
+        DeviceVar& v = var(name);
+        const int64_t n = v.is_csr ? v.nelems_local : v.nrows_local;
+        const int64_t d = v.row_elems;
+        if (n == 0 || d == 0)
+            return at::full({5, d}, std::numeric_limits<double>::quiet_NaN(),
+                            at::TensorOptions().dtype(at::kDouble));
+        auto opts = at::TensorOptions().dtype(at::kDouble).device(at::kCUDA, device_);
+        at::Tensor out = at::empty({5, d}, opts);
+        const size_t sb = ddstore::colstats_scratch_bytes(n, d, v.dds_t);
+        at::Tensor scratch = at::empty({(int64_t)(sb / sizeof(double))}, opts);
+        ddstore::column_stats(stream(), v.base, n, d, v.dds_t, scratch.data_ptr(),
+                              out.data_ptr<double>());
+        return out.cpu();
+    }
+
     void gather_csr(const std::string& name, const at::Tensor& idx,
                     const at::Tensor& out_off, at::Tensor out, int64_t total_elems) {
         RoctxRange rr_("ddstore::gather_csr");
@@ -828,6 +894,44 @@ public:
         v.n_gather += 1;
         v.rows_gathered += nidx;
         // bytes accounted via the device DDS_CTR_ELEMS counter (see query)
+    }
+
+    // gather_csr_padded with one (scale, shift) pair per column of an element.
+    void gather_csr_padded_cols(const std::string& name, const at::Tensor& idx,
+                                at::Tensor out, at::Tensor lengths, int64_t max_len,
+                                int64_t pad_bits, const at::Tensor& scale,
+                                const at::Tensor& shift) {
+        RoctxRange rr_("ddstore::gather_csr_padded_cols");
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.is_csr, "ddstore gather_csr_padded: not a CSR variable");
+        check_peers(v);
+        check_idx(idx);
+        const int64_t nidx = idx.numel();
+        TORCH_CHECK(max_len >= 1, "ddstore gather_csr_padded: max_len must be >= 1");
+        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
+                        out.device().index() == device_,
+                    "ddstore gather_csr_padded: output must be a contiguous tensor "
+                    "on the store device");
+        TORCH_CHECK(out.numel() == nidx * max_len * v.row_elems,
+                    "ddstore gather_csr_padded: shape mismatch");
+        TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.is_contiguous() &&
+                        lengths.device().is_cuda() &&
+                        lengths.device().index() == device_ &&
+                        lengths.numel() == nidx,
+                    "ddstore gather_csr_padded: bad lengths tensor");
+        const int out_t = dds_type_of(out);
+        TORCH_CHECK(out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
+                    "ddstore gather_csr_padded: affine output must be f32/f16/bf16");
+        TORCH_CHECK(v.row_elems >= 1 && v.row_elems < (int64_t(1) << 31) / 16,
+                    "ddstore gather_csr_padded: bad element width for a column affine");
+        ddstore::gather_csr_padded_cols(
+            stream(), (const void* const*)v.d_peers, v.d_prefix, v.d_elem_prefix,
+            nparts_, v.d_goff, v.prefix[nparts_], idx.data_ptr<int64_t>(), nidx,
+            v.row_elems, max_len, v.dds_t, out_t, affine_vec(scale, v.row_elems),
+            affine_vec(shift, v.row_elems), (uint64_t)pad_bits, out.data_ptr(),
+            lengths.data_ptr<int64_t>(), v.d_oob);
+        v.n_gather += 1;
+        v.rows_gathered += nidx;
     }
 
     void csr_lens(const std::string& name, const at::Tensor& idx, at::Tensor lens) {

@@ -61,6 +61,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::arg("max_len"), py::arg("pad_bits"), py::arg("affine") = false,
              py::arg("scale") = 1.0, py::arg("shift") = 0.0,
              py::call_guard<py::gil_scoped_release>())
+        .def("gather_affine_cols", &DeviceStore::gather_affine_cols,
+             py::call_guard<py::gil_scoped_release>())
+        .def("gather_csr_padded_cols", &DeviceStore::gather_csr_padded_cols,
+             py::call_guard<py::gil_scoped_release>())
+        .def("column_stats", &DeviceStore::column_stats,
+             py::call_guard<py::gil_scoped_release>())
         .def("scatter_local", &DeviceStore::scatter_local, py::call_guard<py::gil_scoped_release>())
         .def("local_shard", &DeviceStore::local_shard)
         .def("epoch_begin", &DeviceStore::epoch_begin, py::call_guard<py::gil_scoped_release>())

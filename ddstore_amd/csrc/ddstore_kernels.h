@@ -90,6 +90,19 @@ void gather_rows_affine(hipStream_t stream,
                         float scale, float shift,
                         void* d_out, unsigned long long* d_oob);
 
+// Per-column form of gather_rows_affine: out[r][c] = cast(in[r][c]) *
+// d_scale[c] + d_shift[c], same rounding contract. d_scale and d_shift are
+// device arrays of row_elems floats each, 16-B aligned, on the store device.
+void gather_rows_affine_cols(hipStream_t stream,
+                             const void* const* d_peer_base,
+                             const int64_t* d_prefix,
+                             const void* const* h_peer_base,
+                             const int64_t* h_prefix, int nparts,
+                             const int64_t* d_idx, int64_t nidx,
+                             int64_t row_elems, int in_t, int out_t,
+                             const float* d_scale, const float* d_shift,
+                             void* d_out, unsigned long long* d_oob);
+
 // CSR (variable-length record) gather: sample `g` owns elements
 // [d_goff[g], d_goff[g+1]) of the global element space; each element is
 // `elem_bytes` bytes (= disp * itemsize). Output element offsets per sample
@@ -165,6 +178,35 @@ void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
                        bool affine, float scale, float shift, uint64_t pad_bits,
                        void* d_out, int64_t* d_lengths,
                        unsigned long long* d_ctrs);
+
+// Vector form of gather_csr_padded's affine: column c of every element (its
+// flat position in [0, row_elems)) is scaled by d_scale[c] and shifted by
+// d_shift[c]; arrays as for gather_rows_affine_cols. Everything else,
+// the untouched pad included, as gather_csr_padded with affine = true.
+void gather_csr_padded_cols(hipStream_t stream, const void* const* d_peer_base,
+                            const int64_t* d_sample_prefix,
+                            const int64_t* d_elem_prefix, int nparts,
+                            const int64_t* d_goff, int64_t nsamples_total,
+                            const int64_t* d_idx, int64_t nidx,
+                            int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                            const float* d_scale, const float* d_shift,
+                            uint64_t pad_bits, void* d_out, int64_t* d_lengths,
+                            unsigned long long* d_ctrs);
+
+// Column statistics of one local shard, viewed as a row-major (rows,
+// row_elems) array of dtype `in_t` (for a CSR variable: its elements). Writes
+// d_out[0..5*row_elems): for every column, as f64, a pivot p taken from its
+// values and the offset o with mean = p + o (kept apart so that a merge with
+// another shard's result can difference the means without the rounding of a
+// large mean), M2 = sum((x - mean)^2), min and max; a column with a NaN has
+// NaN in o, M2, min and max. Two kernels on
+// `stream`, deterministic (no atomics), reads only [d_base, d_base + rows *
+// row_elems). d_scratch: colstats_scratch_bytes(...) bytes, no zeroing
+// needed; its size depends on row_elems and the grid, not on `rows`.
+// rows == 0 or row_elems == 0 launches nothing and writes nothing.
+size_t colstats_scratch_bytes(int64_t rows, int64_t row_elems, int in_t);
+void column_stats(hipStream_t stream, const void* d_base, int64_t rows,
+                  int64_t row_elems, int in_t, void* d_scratch, double* d_out);
 
 // Graph-batch fetch (DeviceStore::gather_graph): the pieces beside the node
 // features, which gather_csr_balanced fetches unchanged.

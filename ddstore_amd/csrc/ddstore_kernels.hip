@@ -157,15 +157,21 @@ __device__ __forceinline__ Tout cvt(Tin v) {
 // (data-loader normalization fused into the fetch: store u8/fp8/f16 samples,
 // gather normalized f32/bf16/f16 minibatches in one pass). Math in f32.
 // ---------------------------------------------------------------------------
+// kNeedsCol: the transform wants the element's column (its flat position in
+// the row or CSR element). Only then do the kernels form one, so the other
+// instantiations keep the code they had before the column existed.
 struct XfIdentity {
+    static constexpr bool kNeedsCol = false;
     template <typename Tout, typename Tin>
     __device__ __forceinline__ Tout apply(Tin v) const { return v; }
 };
 struct XfCast {
+    static constexpr bool kNeedsCol = false;
     template <typename Tout, typename Tin>
     __device__ __forceinline__ Tout apply(Tin v) const { return cvt<Tout>(v); }
 };
 struct XfAffine {
+    static constexpr bool kNeedsCol = false;
     float scale, shift;
     // Always 0, but only the host knows. For an f16 output the compiler
     // selects v_fma_mixlo_f16 for fmaf + convert, which rounds the exact sum
@@ -181,6 +187,58 @@ struct XfAffine {
         return cvt<Tout>(y);
     }
 };
+// Per-column affine: out = fma(cast(in), scale[col], shift[col]), the same
+// contract as XfAffine with one (scale, shift) pair per column. The vectors
+// hold `disp` floats each, 16-B aligned (the host checks), and are read
+// through the cache, as aligned vector loads wherever a chunk lies in one row.
+//
+// Cache against LDS (both vectors staged once per persistent block of the
+// tiled kernel), MI355X, flagship shape (262,144 x 128 f32 -> bf16, 4 rotating
+// outputs and index sets): 34.7 us per fetch through the cache, 34.8 us from
+// LDS, the scalar XfAffine 34.9 / 35.7 us in the same two runs -- equal within
+// the spread between repetitions (0.3 to 2.8 us). The cache form has no cap
+// on the row length and no barrier, so it stayed and the LDS variant was
+// taken out again (profiles/colnorm_ab.txt).
+struct XfAffineCol {
+    static constexpr bool kNeedsCol = true;
+    const float* scale;
+    const float* shift;
+    uint32_t opaque_zero = 0;  // see XfAffine
+    template <typename Tout, typename Tin>
+    __device__ __forceinline__ Tout apply(Tin v, float sc, float sh) const {
+        float y = fmaf(cvt<float>(v), sc, sh);
+        if constexpr (std::is_same_v<Tout, __half>)
+            y = __uint_as_float(__float_as_uint(y) | opaque_zero);
+        return cvt<Tout>(y);
+    }
+};
+
+// One VEC-element chunk through `xf`. For a column transform, `col0` is the
+// column of the chunk's first element and sc/sh the two vectors; CONTIG says that col0 is a multiple of VEC and the chunk lies inside
+// one row, so the VEC scales and shifts are one aligned vector load each.
+// Without CONTIG the column wraps to 0 at `disp`, element by element.
+template <typename Tout, int VEC, bool CONTIG, typename Xf, typename Tin>
+__device__ __forceinline__ void xf_chunk(const Xf& xf, const float* sc, const float* sh,
+                                         const VecT<Tin, VEC>& vin, VecT<Tout, VEC>& vout,
+                                         uint32_t col0, uint32_t disp = 0) {
+    if constexpr (!Xf::kNeedsCol) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) vout.v[k] = xf.template apply<Tout>(vin.v[k]);
+    } else if constexpr (CONTIG) {
+        const VecT<float, VEC> s = *reinterpret_cast<const VecT<float, VEC>*>(sc + col0);
+        const VecT<float, VEC> h = *reinterpret_cast<const VecT<float, VEC>*>(sh + col0);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k)
+            vout.v[k] = xf.template apply<Tout>(vin.v[k], s.v[k], h.v[k]);
+    } else {
+        uint32_t cc = col0;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            vout.v[k] = xf.template apply<Tout>(vin.v[k], sc[cc], sh[cc]);
+            cc = cc + 1 == disp ? 0 : cc + 1;
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------
 // One-shot fixed-stride row gather: thread t moves VEC-element chunk
@@ -227,8 +285,11 @@ k_gather_oneshot(const void* const* peer_base, const int64_t* gprefix, int npart
         const Vin vin = *reinterpret_cast<const Vin*>(
             dir.base[p] + (g - dir.prefix[0][p]) * row_elems + c * VEC);
         Vout vout;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) vout.v[k] = xf.template apply<Tout>(vin.v[k]);
+        if constexpr (Xf::kNeedsCol)  // a chunk never leaves its row
+            xf_chunk<Tout, VEC, true>(xf, xf.scale, xf.shift, vin, vout,
+                                      (uint32_t)c * VEC);
+        else
+            xf_chunk<Tout, VEC, true>(xf, nullptr, nullptr, vin, vout, 0u);
         *reinterpret_cast<Vout*>(out + t * VEC) = vout;
     }
 }
@@ -313,6 +374,16 @@ constexpr int tiled_unroll() {
     return INB >= 128 ? 1 : (128 / INB > 8 ? 8 : 128 / INB);
 }
 
+// What k_gather_tiled keeps for a column transform: the scales and shifts of
+// the U chunks in flight. Empty for every other transform, so those
+// instantiations carry nothing of it.
+template <typename Xf, int VEC, int U, bool = Xf::kNeedsCol>
+struct TiledCols {};
+template <typename Xf, int VEC, int U>
+struct TiledCols<Xf, VEC, U, true> {
+    VecT<float, VEC> s[U], h[U];
+};
+
 template <typename Tin, typename Tout, typename Xf, bool LDSDIR>
 __global__ void __launch_bounds__(kBlock)
 k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
@@ -328,6 +399,7 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
     __shared__ LdsDir<uintptr_t> ldir;  // unused, so not allocated, without LDSDIR
     if constexpr (LDSDIR) ldir.load(peer_base, nparts, gprefix);
     const int64_t total = LDSDIR ? ldir.prefix[0][nparts] : dir.prefix[DDS_DIR_KPARTS];
+    TiledCols<Xf, VEC, U> tc;  // an empty object unless xf wants columns
 
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -391,6 +463,13 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
                 for (int u = 0; u < U; ++u) {
                     const uintptr_t sp =
                         (uintptr_t)__shfl((unsigned long long)src, (int)(rl & 63u));
+                    // A column transform's scales and shifts are fetched AHEAD
+                    // of the payload: loads return in order, so a vector load
+                    // issued at the convert would wait for every payload load.
+                    if constexpr (Xf::kNeedsCol) {
+                        tc.s[u] = *reinterpret_cast<const VecT<float, VEC>*>(xf.scale + c * VEC);
+                        tc.h[u] = *reinterpret_cast<const VecT<float, VEC>*>(xf.shift + c * VEC);
+                    }
                     vin[u] = load_global<Vin>(sp + (uintptr_t)(c * (uint32_t)INB));
                     c += r64;
                     rl += q64;
@@ -402,9 +481,16 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     Vout vout;
+                    if constexpr (Xf::kNeedsCol) {
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k)
-                        vout.v[k] = xf.template apply<Tout>(vin[u].v[k]);
+                        for (int k = 0; k < VEC; ++k)
+                            vout.v[k] = xf.template apply<Tout>(vin[u].v[k], tc.s[u].v[k],
+                                                                tc.h[u].v[k]);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k)
+                            vout.v[k] = xf.template apply<Tout>(vin[u].v[k]);
+                    }
                     store_out(&op[jb + 64u * u + lane], vout);
                 }
             } else {
@@ -420,9 +506,14 @@ k_gather_tiled(const GatherDirK dir, const void* const* peer_base,
                         const Vin v =
                             load_global<Vin>(sp + (uintptr_t)(c * (uint32_t)INB));
                         Vout vout;
+                        if constexpr (Xf::kNeedsCol) {
+                            xf_chunk<Tout, VEC, true>(xf, xf.scale, xf.shift, v, vout,
+                                                      c * (uint32_t)VEC);
+                        } else {
 #pragma unroll
-                        for (int k = 0; k < VEC; ++k)
-                            vout.v[k] = xf.template apply<Tout>(v.v[k]);
+                            for (int k = 0; k < VEC; ++k)
+                                vout.v[k] = xf.template apply<Tout>(v.v[k]);
+                        }
                         store_out(&op[j], vout);
                     }
                     c += r64;
@@ -943,6 +1034,19 @@ k_gather_csr_padded(const void* const* peer_base, const int64_t* sample_prefix,
     const int64_t step = (int64_t)gridDim.x * (kBlock >> lg_group);
     const int64_t row_elems = max_len * disp;
     const int64_t cpr = row_elems / VEC;  // chunks per output row
+    // Column transform: element e of a row sits in column e % disp. A lane
+    // starts at chunk `tid` and steps by `group` chunks, so two divides per
+    // thread set up a walk that needs only an add and a compare per chunk.
+    const float* csc = nullptr;
+    const float* csh = nullptr;
+    uint32_t d32 = 0, col0 = 0, cstep = 0;
+    if constexpr (Xf::kNeedsCol) {
+        csc = xf.scale;
+        csh = xf.shift;
+        d32 = (uint32_t)disp;
+        col0 = (uint32_t)(((uint32_t)tid * (uint32_t)VEC) % d32);
+        cstep = (uint32_t)(((uint32_t)group * (uint32_t)VEC) % d32);
+    }
     if (blockIdx.x < kPadCountBlocks)  // block-uniform
         count_padded(dir, nparts, goff, idx, nidx, max_len, s_acc, ctrs);
     for (int64_t s = first; s < nidx; s += step) {
@@ -961,29 +1065,39 @@ k_gather_csr_padded(const void* const* peer_base, const int64_t* sample_prefix,
             if (tid == 0) lengths[s] = len;
         }
         Vout* __restrict__ op = reinterpret_cast<Vout*>(out + s * row_elems);
+        uint32_t col = col0;  // column of element c * VEC, kept without a divide
         for (int64_t c = tid; c < cpr; c += group) {
             const int64_t e = c * VEC;
             Vout vout = vpad;
             if (e < nvalid) {
                 if (VEC == 1 || aligned) {
                     const Vin vin = *reinterpret_cast<const Vin*>(sp + e);
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k)
-                        vout.v[k] = xf.template apply<Tout>(vin.v[k]);
+                    xf_chunk<Tout, VEC, true>(xf, csc, csh, vin, vout, col);
                 } else if (e + VEC <= nvalid) {
-                    Tin x[VEC];
+                    Vin x;
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) x[k] = sp[e + k];
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k)
-                        vout.v[k] = xf.template apply<Tout>(x[k]);
+                    for (int k = 0; k < VEC; ++k) x.v[k] = sp[e + k];
+                    xf_chunk<Tout, VEC, false>(xf, csc, csh, x, vout, col, d32);
                 } else {  // the chunk on the valid/pad boundary
+                    uint32_t cc = col;
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k)
-                        if (e + k < nvalid) vout.v[k] = xf.template apply<Tout>(sp[e + k]);
+                    for (int k = 0; k < VEC; ++k) {
+                        if (e + k < nvalid) {
+                            if constexpr (Xf::kNeedsCol)
+                                vout.v[k] = xf.template apply<Tout>(sp[e + k], csc[cc],
+                                                                    csh[cc]);
+                            else
+                                vout.v[k] = xf.template apply<Tout>(sp[e + k]);
+                        }
+                        if constexpr (Xf::kNeedsCol) cc = cc + 1 == d32 ? 0 : cc + 1;
+                    }
                 }
             }
             op[c] = vout;
+            if constexpr (Xf::kNeedsCol) {
+                col += cstep;
+                if (col >= d32) col -= d32;
+            }
         }
     }
 }
@@ -1207,6 +1321,248 @@ k_scatter_rows(V* __restrict__ base, int64_t nrows, int64_t chunks_per_row,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Column statistics of the local shard: per column of the row-major (R, D)
+// view, the mean, the centred sum of squares M2, min and max, all in f64.
+//
+// Numerics: shifted sums. Every column has a pivot p -- the median of its
+// values in rows 0, R/2 and R-1 (0 if that is not finite) -- and the kernel
+// accumulates S1 = sum(x - p) and S2 = sum((x - p)^2). Then mean = p + S1/n
+// and M2 = S2 - S1^2/n, whose cancellation is 1 + (mean - p)^2/var: a small
+// number for a pivot taken from the data, however large the mean is against
+// the spread (the raw-moment form has (mean/std)^2 there). A constant column
+// has x - p == 0 everywhere, so M2 == 0 exactly. All blocks use the same
+// pivots, so partials combine by plain addition, in a fixed order: two calls
+// give the same bits. No floating-point atomics anywhere.
+//
+// NaN: v_min_f64/v_max_f64 drop NaNs, so every slot keeps a NaN flag; after
+// the loop a flagged slot's min and max become NaN, and every later combine
+// step propagates a NaN. The sums turn NaN by themselves. (Deciding from the
+// sum alone would also call a column with +inf and -inf a NaN column.)
+//
+// Mapping: the shard is one flat array of N = R * D elements, read in chunks
+// of VEC elements (16 B; 8 B for 1-byte types, which caps a thread at 8
+// slots). Active thread t of S takes chunks t, t + S, t + 2S, ...; S is a
+// multiple of D / gcd(D, VEC), so S * VEC is a multiple of D and slot j of
+// thread t only ever sees column (t * VEC + j) % D: five f64 registers per
+// slot (pivot, S1, S2, min, max), no column arithmetic in the loop. Chunks
+// are aligned in the flat view whatever D is (D = 3 of f32 loads dwordx4).
+// The grid has at least D / gcd(D, VEC) threads; for a D beyond the
+// 256 * VEC positions one block covers, blocks own different column ranges
+// (a whole image per row: 150528 u8 columns over 74 blocks).
+//
+// Per block: the 256 * VEC slots are folded in LDS by column with a fixed
+// tree (slots e, e + D, e + 2D, ... share a column), leaving nb = min(D,
+// 256 * VEC) entries; entry e of block b is column (b * 256 * VEC + e) % D.
+// k_colstats_final folds the blocks of each column in block order and
+// finalizes. Scratch: colstats_scratch_bytes = blocks * nb * 4 doubles,
+// independent of R.
+//
+// Measured on MI355X, 4 GiB f32 shard of 128 columns: 1.0 ms per call with
+// the read-back, 4.3 TB/s read, fixed-stride and CSR alike; torch.var_mean +
+// torch.aminmax over a .double() copy: 9.2 ms and 8.1 GiB extra
+// (profiles/colnorm_ab.txt). The grid (4 blocks per CU, U = 4 loads in
+// flight) was chosen by construction and not swept.
+// ---------------------------------------------------------------------------
+template <typename T>
+constexpr int stat_vec() {
+    return sizeof(T) == 1 ? 8 : 16 / (int)sizeof(T);
+}
+
+template <typename T>
+__device__ __forceinline__ double stat_f64(T v) {
+    if constexpr (std::is_same_v<T, __half>) return (double)__half2float(v);
+    else if constexpr (std::is_same_v<T, __hip_bfloat16>) return (double)__bfloat162float(v);
+    else if constexpr (is_fp8_v<T>) return (double)static_cast<float>(v);
+    else return (double)v;  // i64 rounds to nearest
+}
+
+template <typename T>
+__device__ __forceinline__ double stat_pivot(const T* __restrict__ base, int64_t R,
+                                             int64_t D, int64_t c) {
+    const double a = stat_f64(base[c]);
+    const double b = stat_f64(base[(R / 2) * D + c]);
+    const double d = stat_f64(base[(R - 1) * D + c]);
+    const double m = fmax(fmin(a, b), fmin(fmax(a, b), d));
+    return fabs(m) <= 1.7976931348623157e308 ? m : 0.0;  // a NaN fails too
+}
+
+// quantity Q of a partial: 0 = S1, 1 = S2 (sums), 2 = min, 3 = max (a NaN in
+// either operand stays)
+template <int Q>
+__device__ __forceinline__ double stat_combine(double a, double b) {
+    if constexpr (Q < 2) {
+        return a + b;
+    } else {
+        const double r = Q == 2 ? fmin(a, b) : fmax(a, b);
+        return (a != a || b != b) ? __builtin_nan("") : r;
+    }
+}
+
+template <int Q>
+__device__ __forceinline__ double stat_identity() {
+    return Q < 2 ? 0.0 : (Q == 2 ? __builtin_inf() : -__builtin_inf());
+}
+
+// Fold quantity Q of the block's 256 * VEC slots by column and write the nb
+// entries of this block.
+template <int Q, int VEC>
+__device__ __forceinline__ void stat_block_fold(double* s_stage, const double (&val)[VEC],
+                                                int64_t D, int64_t nb,
+                                                double* __restrict__ part) {
+    constexpr int64_t W = (int64_t)kBlock * VEC;
+    __syncthreads();  // the previous quantity has been read
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s_stage[threadIdx.x * VEC + j] = val[j];
+    __syncthreads();
+    if (D < W) {  // block-uniform
+        int64_t step = 1;
+        while (step * D < W) step <<= 1;  // a power of two >= the replicas
+        for (step >>= 1; step >= 1; step >>= 1) {
+            const int64_t far = step * D;
+            const int64_t lim = far < W - far ? far : W - far;
+            for (int64_t i = threadIdx.x; i < lim; i += kBlock)
+                s_stage[i] = stat_combine<Q>(s_stage[i], s_stage[i + far]);
+            __syncthreads();
+        }
+    }
+    double* __restrict__ dst = part + ((int64_t)Q * gridDim.x + blockIdx.x) * nb;
+    for (int64_t e = threadIdx.x; e < nb; e += kBlock) dst[e] = s_stage[e];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_colstats_partial(const T* __restrict__ base, int64_t R, int64_t D, int64_t S,
+                   int64_t nb, double* __restrict__ part) {
+    constexpr int VEC = stat_vec<T>();
+    constexpr int U = 4;  // loads in flight per thread
+    using V = VecT<T, VEC>;
+    __shared__ double s_stage[kBlock * VEC];
+    const int64_t N = R * D;
+    const int64_t nfull = N / VEC;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+
+    double pv[VEC], acc[4][VEC];
+    uint32_t nanf = 0;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        pv[j] = 0.0;
+        acc[0][j] = 0.0;
+        acc[1][j] = 0.0;
+        acc[2][j] = __builtin_inf();
+        acc[3][j] = -__builtin_inf();
+    }
+    auto take = [&](int j, T raw) {
+        const double x = stat_f64(raw);
+        const double d = x - pv[j];
+        acc[0][j] += d;
+        acc[1][j] = fma(d, d, acc[1][j]);
+        acc[2][j] = fmin(acc[2][j], x);
+        acc[3][j] = fmax(acc[3][j], x);
+        if constexpr (!std::is_integral_v<T>) nanf |= (x != x) ? (1u << j) : 0u;
+    };
+    if (t < S) {
+        int64_t cc = (t * VEC) % D;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            pv[j] = stat_pivot(base, R, D, cc);
+            cc = cc + 1 == D ? 0 : cc + 1;
+        }
+        const V* __restrict__ vb = reinterpret_cast<const V*>(base);
+        int64_t k = t;
+        for (; k + (U - 1) * S < nfull; k += U * S) {
+            V v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = vb[k + u * S];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) take(j, v[u].v[j]);
+        }
+        for (; k < nfull; k += S) {
+            const V v = vb[k];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) take(j, v.v[j]);
+        }
+        if (k == nfull) {  // the last, partial chunk: element loads, in bounds
+#pragma unroll
+            for (int j = 0; j < VEC; ++j)
+                if (nfull * VEC + j < N) take(j, base[nfull * VEC + j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+        if (nanf & (1u << j)) acc[2][j] = acc[3][j] = __builtin_nan("");
+    stat_block_fold<0, VEC>(s_stage, acc[0], D, nb, part);
+    stat_block_fold<1, VEC>(s_stage, acc[1], D, nb, part);
+    stat_block_fold<2, VEC>(s_stage, acc[2], D, nb, part);
+    stat_block_fold<3, VEC>(s_stage, acc[3], D, nb, part);
+}
+
+// One column per lane of 32, the blocks of the partial kernel in 8 slices:
+// each slice folds its blocks in block order, lane group 0 folds the slices
+// in slice order and writes out[0..4][c] = pivot, S1/n (mean = their sum), M2,
+// min, max.
+constexpr int kStatCols = 32;
+constexpr int kStatSlices = kBlock / kStatCols;
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_colstats_final(const T* __restrict__ base, int64_t R, int64_t D,
+                 const double* __restrict__ part, int64_t nblocks, int64_t nb,
+                 double* __restrict__ out) {
+    constexpr int64_t W = (int64_t)kBlock * stat_vec<T>();
+    __shared__ double s_red[4][kStatSlices][kStatCols];
+    const int cl = threadIdx.x % kStatCols;
+    const int sl = threadIdx.x / kStatCols;
+    const int64_t c = (int64_t)blockIdx.x * kStatCols + cl;
+    double a0 = stat_identity<0>(), a1 = stat_identity<1>(), a2 = stat_identity<2>(),
+           a3 = stat_identity<3>();
+    if (c < D) {
+        const int64_t per = (nblocks + kStatSlices - 1) / kStatSlices;
+        const int64_t b0 = sl * per;
+        const int64_t b1 = b0 + per < nblocks ? b0 + per : nblocks;
+        const int64_t wm = W % D;
+        int64_t off = (b0 * wm) % D;  // first column of block b, (b * W) % D
+        for (int64_t b = b0; b < b1; ++b) {
+            int64_t e = c - off;
+            if (e < 0) e += D;
+            if (e < nb) {
+                a0 = stat_combine<0>(a0, part[(0 * nblocks + b) * nb + e]);
+                a1 = stat_combine<1>(a1, part[(1 * nblocks + b) * nb + e]);
+                a2 = stat_combine<2>(a2, part[(2 * nblocks + b) * nb + e]);
+                a3 = stat_combine<3>(a3, part[(3 * nblocks + b) * nb + e]);
+            }
+            off += wm;
+            if (off >= D) off -= D;
+        }
+    }
+    s_red[0][sl][cl] = a0;
+    s_red[1][sl][cl] = a1;
+    s_red[2][sl][cl] = a2;
+    s_red[3][sl][cl] = a3;
+    __syncthreads();
+    if (sl == 0 && c < D) {
+        for (int s = 1; s < kStatSlices; ++s) {
+            a0 = stat_combine<0>(a0, s_red[0][s][cl]);
+            a1 = stat_combine<1>(a1, s_red[1][s][cl]);
+            a2 = stat_combine<2>(a2, s_red[2][s][cl]);
+            a3 = stat_combine<3>(a3, s_red[3][s][cl]);
+        }
+        // The mean leaves as the pair (pivot, S1/n): the host adds the two
+        // only after the cross-rank merge, whose difference of means would
+        // otherwise carry the rounding of a large mean into M2.
+        const double n = (double)R;
+        double m2 = a1 - a0 * (a0 / n);
+        if (m2 < 0.0) m2 = 0.0;  // rounding only; a NaN stays
+        out[c] = stat_pivot(base, R, D, c);
+        out[D + c] = a0 / n;
+        out[2 * D + c] = m2;
+        out[3 * D + c] = a2;
+        out[4 * D + c] = a3;
+    }
+}
+
 inline int dds_itemsize(int t) {
     switch (t) {
         case DDS_U8: case DDS_F8E4M3: case DDS_F8E5M2: return 1;
@@ -1425,6 +1781,31 @@ void gather_rows_affine(hipStream_t stream,
     });
 }
 
+void gather_rows_affine_cols(hipStream_t stream,
+                             const void* const* d_peer_base,
+                             const int64_t* d_prefix,
+                             const void* const* h_peer_base,
+                             const int64_t* h_prefix, int nparts,
+                             const int64_t* d_idx, int64_t nidx,
+                             int64_t row_elems, int in_t, int out_t,
+                             const float* d_scale, const float* d_shift,
+                             void* d_out, unsigned long long* d_oob) {
+    if (nidx == 0 || row_elems == 0) return;
+    const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
+    dispatch_dtype(in_t, [&](auto ti) {
+        dispatch_dtype(out_t, [&](auto to) {
+            using Tin = typename decltype(ti)::type;
+            using Tout = typename decltype(to)::type;
+            // float outputs only
+            if constexpr (std::is_same_v<Tout, float> || std::is_same_v<Tout, __half> ||
+                          std::is_same_v<Tout, __hip_bfloat16>)
+                launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems,
+                                         XfAffineCol{d_scale, d_shift}, (Tout*)d_out,
+                                         d_oob);
+        });
+    });
+}
+
 void gather_rows(hipStream_t stream,
                  const void* const* d_peer_base,
                  const int64_t* d_prefix,
@@ -1536,15 +1917,18 @@ void gather_csr(hipStream_t stream,
     }
 }
 
-void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
-                       const int64_t* d_sample_prefix,
-                       const int64_t* d_elem_prefix, int nparts,
-                       const int64_t* d_goff, int64_t nsamples_total,
-                       const int64_t* d_idx, int64_t nidx,
-                       int64_t row_elems, int64_t max_len, int in_t, int out_t,
-                       bool affine, float scale, float shift, uint64_t pad_bits,
-                       void* d_out, int64_t* d_lengths,
-                       unsigned long long* d_ctrs) {
+// Both forms of the padded gather: `affine` false = byte move or cast, true =
+// the scalar pair, or the per-column vectors if d_scale is not null.
+static void csr_padded_impl(hipStream_t stream, const void* const* d_peer_base,
+                            const int64_t* d_sample_prefix,
+                            const int64_t* d_elem_prefix, int nparts,
+                            const int64_t* d_goff, int64_t nsamples_total,
+                            const int64_t* d_idx, int64_t nidx,
+                            int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                            bool affine, float scale, float shift,
+                            const float* d_scale, const float* d_shift,
+                            uint64_t pad_bits, void* d_out, int64_t* d_lengths,
+                            unsigned long long* d_ctrs) {
     if (nidx == 0) return;
     if (row_elems == 0 || max_len == 0) {
         // no payload to move: lengths and the bad-index count only
@@ -1605,9 +1989,93 @@ void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
                                  std::is_same_v<Tout, __half> ||
                                  std::is_same_v<Tout, __hip_bfloat16>) {
                 // float outputs only
-                launch_xf(ti, to, XfAffine{scale, shift});
+                if (d_scale)
+                    launch_xf(ti, to, XfAffineCol{d_scale, d_shift});
+                else
+                    launch_xf(ti, to, XfAffine{scale, shift});
             }
         });
+    });
+}
+
+void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
+                       const int64_t* d_sample_prefix,
+                       const int64_t* d_elem_prefix, int nparts,
+                       const int64_t* d_goff, int64_t nsamples_total,
+                       const int64_t* d_idx, int64_t nidx,
+                       int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                       bool affine, float scale, float shift, uint64_t pad_bits,
+                       void* d_out, int64_t* d_lengths,
+                       unsigned long long* d_ctrs) {
+    csr_padded_impl(stream, d_peer_base, d_sample_prefix, d_elem_prefix, nparts, d_goff,
+                    nsamples_total, d_idx, nidx, row_elems, max_len, in_t, out_t, affine,
+                    scale, shift, nullptr, nullptr, pad_bits, d_out, d_lengths, d_ctrs);
+}
+
+void gather_csr_padded_cols(hipStream_t stream, const void* const* d_peer_base,
+                            const int64_t* d_sample_prefix,
+                            const int64_t* d_elem_prefix, int nparts,
+                            const int64_t* d_goff, int64_t nsamples_total,
+                            const int64_t* d_idx, int64_t nidx,
+                            int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                            const float* d_scale, const float* d_shift,
+                            uint64_t pad_bits, void* d_out, int64_t* d_lengths,
+                            unsigned long long* d_ctrs) {
+    csr_padded_impl(stream, d_peer_base, d_sample_prefix, d_elem_prefix, nparts, d_goff,
+                    nsamples_total, d_idx, nidx, row_elems, max_len, in_t, out_t, true,
+                    0.0f, 0.0f, d_scale, d_shift, pad_bits, d_out, d_lengths, d_ctrs);
+}
+
+// ---- column statistics (kernels: k_colstats_partial / k_colstats_final) ----
+namespace {
+struct StatPlan {
+    int64_t blocks, S, nb;
+};
+// The grid of the partial kernel. Scratch formula: blocks * nb partial
+// entries of 4 doubles (S1, S2, min, max), nb = min(D, 256 * VEC) -- a
+// function of D and the grid only, never of the number of rows.
+StatPlan stat_plan(int64_t rows, int64_t D, int in_t) {
+    const int isz = dds_itemsize(in_t);
+    const int64_t vec = isz == 1 ? 8 : 16 / isz;
+    int64_t g = D, h = vec;  // gcd(D, vec)
+    while (h) {
+        const int64_t r = g % h;
+        g = h;
+        h = r;
+    }
+    const int64_t dp = D / g;  // S is a multiple of this
+    const int64_t nchunks = (rows * D + vec - 1) / vec;
+    // >= 32 chunks per thread before the grid grows, 4 blocks per CU at most
+    int64_t b = nchunks / ((int64_t)kBlock * 32);
+    const int64_t target = (int64_t)cu_count() * 4;
+    if (b > target) b = target;
+    if (b < 1) b = 1;
+    const int64_t need = (dp + kBlock - 1) / kBlock;  // every column has a thread
+    if (b < need) b = need;
+    const int64_t W = (int64_t)kBlock * vec;
+    return StatPlan{b, (b * kBlock / dp) * dp, D < W ? D : W};
+}
+}  // namespace
+
+size_t colstats_scratch_bytes(int64_t rows, int64_t row_elems, int in_t) {
+    if (rows <= 0 || row_elems <= 0) return 0;
+    const StatPlan p = stat_plan(rows, row_elems, in_t);
+    return (size_t)(p.blocks * p.nb * 4) * sizeof(double);
+}
+
+void column_stats(hipStream_t stream, const void* d_base, int64_t rows,
+                  int64_t row_elems, int in_t, void* d_scratch, double* d_out) {
+    if (rows <= 0 || row_elems <= 0) return;
+    const StatPlan p = stat_plan(rows, row_elems, in_t);
+    const int64_t fb = (row_elems + kStatCols - 1) / kStatCols;
+    dispatch_dtype(in_t, [&](auto ti) {
+        using T = typename decltype(ti)::type;
+        hipLaunchKernelGGL((k_colstats_partial<T>), dim3((unsigned)p.blocks),
+                           dim3(kBlock), 0, stream, (const T*)d_base, rows, row_elems,
+                           p.S, p.nb, (double*)d_scratch);
+        hipLaunchKernelGGL((k_colstats_final<T>), dim3((unsigned)fb), dim3(kBlock), 0,
+                           stream, (const T*)d_base, rows, row_elems,
+                           (const double*)d_scratch, p.blocks, p.nb, d_out);
     });
 }
 

@@ -41,6 +41,9 @@ class PrefetchLoader:
               (e.g. the ids a DistributedSampler assigned to this rank)
     batch_size : int      rows per yielded batch
     out_dtype : optional  fused dtype cast in the gather kernel
+    affine : optional     ``(scale, shift)`` fused into the fetch as in
+                          ``get_batch``: numbers, or vectors of ``disp`` values
+                          for per-column normalization (converted once, here)
     label_name : optional second variable gathered with the same indices
     depth : int           ring depth (2 = classic double buffering)
     drop_last : bool
@@ -73,7 +76,9 @@ class PrefetchLoader:
         # under a multi-ms train step against timing noise)
         self.collect_events = collect_events
         self.fetch_events: list = []
-        self.affine = affine
+        # per-column operands become device float32 vectors here, once, and
+        # every batch's fetch uses them as they are
+        self.affine = None if affine is None else store.prepare_affine(name, affine)
         if depth is None:
             depth = int(os.environ.get("DDSTORE_PREFETCH_DEPTH", "2"))
         self.store = store

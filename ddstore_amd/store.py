@@ -65,6 +65,47 @@ class GraphBatch(NamedTuple):
     edge_extras: tuple
 
 
+class ColumnStats(NamedTuple):
+    """Per-column statistics of a variable, as :meth:`DDStore.column_stats`
+    returns them. Column ``c`` is flat position ``c`` of a row (CSR: of an
+    element)."""
+
+    count: int            # rows (CSR: elements) the statistics cover
+    mean: torch.Tensor    # CPU float64 (disp,)
+    std: torch.Tensor     # population standard deviation (divide by count)
+    min: torch.Tensor
+    max: torch.Tensor
+
+    def affine(self, kind: str = "standard") -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(scale, shift)`` as CPU float32 vectors for the ``affine=``
+        argument of the fetches, computed in float64 and rounded once.
+        ``"standard"``: ``(x - mean) / std``; ``"minmax"``: ``(x - min) /
+        (max - min)``. A column without spread (``std == 0`` or ``max ==
+        min``) gets ``scale = 1`` and ``shift = -mean`` (``-min``): it maps to
+        0, not to inf."""
+        if kind == "standard":
+            center, spread = self.mean, self.std
+        elif kind == "minmax":
+            center, spread = self.min, self.max - self.min
+        else:
+            raise ValueError(f"ColumnStats.affine: unknown kind '{kind}'")
+        safe = torch.where(spread == 0, torch.ones_like(spread), spread)
+        return (1.0 / safe).to(torch.float32), (-center / safe).to(torch.float32)
+
+
+def _affine_vector(a) -> Optional[torch.Tensor]:
+    """The vector form of one affine operand as a tensor, None for a number
+    (Python or NumPy scalar, 0-d array or tensor)."""
+    if isinstance(a, torch.Tensor):
+        return a if a.dim() >= 1 else None
+    if isinstance(a, (int, float, np.generic)):
+        return None
+    arr = np.asarray(a)
+    if arr.ndim == 0:
+        return None
+    return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def _as_tensor(arr: ArrayLike) -> torch.Tensor:
     if isinstance(arr, torch.Tensor):
         t = arr
@@ -350,6 +391,40 @@ class DDStore:
                 f"('{name}' holds {self._vars[name]['dtype']}); fetch it as is "
                 "and compare with 0")
 
+    def _affine_operands(self, what: str, name: str, affine):
+        """``(scale, shift, per_column)`` of an ``affine=`` argument: two
+        floats, or -- if either operand is a vector of ``disp`` values, the
+        other being broadcast -- two contiguous float32 tensors on the store
+        device. A tensor that already is one is used as it is (no copy, no
+        sync), so the result can be passed again at no cost."""
+        disp = self._meta(name)["disp"]
+        vecs = [_affine_vector(a) for a in (affine[0], affine[1])]
+        if vecs[0] is None and vecs[1] is None:
+            return float(affine[0]), float(affine[1]), False
+        out = []
+        for a, v in zip((affine[0], affine[1]), vecs):
+            if v is None:
+                v = torch.full((disp,), float(a), dtype=torch.float32, device=self.device)
+            elif v.dim() != 1 or v.numel() != disp:
+                raise ValueError(
+                    f"ddstore {what}: a per-column affine operand must hold "
+                    f"disp = {disp} values, got shape {tuple(v.shape)}")
+            elif not (v.dtype == torch.float32 and v.device == self.device
+                      and v.is_contiguous()):
+                v = v.to(device=self.device, dtype=torch.float32).contiguous()
+            if self.mode == "hip" and v.data_ptr() % 16:
+                v = v.clone()  # the kernels load the vectors 16 B at a time
+            out.append(v)
+        return out[0], out[1], True
+
+    def prepare_affine(self, name: str, affine):
+        """Convert an ``affine=(scale, shift)`` argument for variable ``name``
+        once: per-column operands become float32 tensors on the store device,
+        which the fetches then use as they are. A scalar pair comes back as
+        two floats."""
+        scale, shift, _ = self._affine_operands("prepare_affine", name, affine)
+        return scale, shift
+
     def get(self, name: str, out: ArrayLike, start: int = 0) -> None:
         """Reference-compatible dense read: fills ``out`` with rows
         ``[start, start+len(out))``; the range may not cross a shard boundary
@@ -383,7 +458,11 @@ class DDStore:
         ``affine=(scale, shift)`` fuses ``out = cast(row) * scale + shift``
         (f32 math, float output dtypes) into the gather -- data-loader
         normalization without a second pass (e.g. u8 pixels -> normalized
-        bf16)."""
+        bf16). Each of ``scale`` and ``shift`` is a number or a 1-D vector of
+        ``disp`` values (``out[:, c] = cast(row[c]) * scale[c] + shift[c]``,
+        per-feature normalization; see :meth:`column_stats`); a number beside
+        a vector is broadcast, any other length raises ``ValueError``. Vectors
+        that are float32 tensors on the store device are used as they are."""
         meta = self._meta(name)
         idx = torch.as_tensor(indices, dtype=torch.int64)
         idx = idx.to(self.device, non_blocking=True).contiguous()
@@ -396,11 +475,14 @@ class DDStore:
             )
         self._account(meta, idx)
         if affine is not None:
-            scale, shift = float(affine[0]), float(affine[1])
+            scale, shift, per_col = self._affine_operands("get_batch", name, affine)
             if out.dtype not in (torch.float32, torch.float16, torch.bfloat16):
                 raise TypeError("ddstore get_batch: affine output must be float")
             if self.mode == "hip":
-                self._backend.gather_affine(name, idx, out, scale, shift)
+                if per_col:
+                    self._backend.gather_affine_cols(name, idx, out, scale, shift)
+                else:
+                    self._backend.gather_affine(name, idx, out, scale, shift)
             else:
                 tmp = torch.empty((n, meta["disp"]), dtype=meta["dtype"])
                 self._backend.gather(name, idx, tmp)
@@ -504,8 +586,9 @@ class DDStore:
                     "ddstore get_csr_padded: out must be a contiguous "
                     f"{out_dtype} tensor of {n}*{max_len}*{disp} elements on "
                     "the store device")
+        per_col = False
         if affine is not None:
-            scale, shift = float(affine[0]), float(affine[1])
+            scale, shift, per_col = self._affine_operands("get_csr_padded", name, affine)
             if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
                 raise TypeError("ddstore get_csr_padded: affine output must be float")
         pad = torch.tensor([pad_value], dtype=out_dtype)  # converted once, on the host
@@ -522,7 +605,10 @@ class DDStore:
             # the pad travels as the raw bits of one output element
             bits_t = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
             pad_bits = int(pad.view(bits_t[pad.element_size()]).item())
-            if affine is not None:
+            if per_col:
+                self._backend.gather_csr_padded_cols(name, idx, dense, lengths,
+                                                     max_len, pad_bits, scale, shift)
+            elif affine is not None:
                 self._backend.gather_csr_padded(name, idx, dense, lengths, max_len,
                                                 pad_bits, True, scale, shift)
             else:
@@ -783,6 +869,86 @@ class DDStore:
         """Zero-copy view of this rank's shard (rows x disp). Valid until
         ``free``."""
         return self._backend.local_shard(name)
+
+    # -------------------------------------------------------------- statistics
+    def _column_stats_host(self, name: str, n: int, disp: int) -> torch.Tensor:
+        """Host form of the native ``column_stats``: (5, disp) float64 =
+        pivot, offset (mean = pivot + offset), M2, min, max of the local
+        shard. The pivot is the first row (0 where that is not finite); the
+        offset is the mean of ``x - pivot`` and M2 the sum of the squares
+        centred on it, so nothing is left to cancel."""
+        if n == 0 or disp == 0:
+            return torch.full((5, disp), float("nan"), dtype=torch.float64)
+        x = self._backend.local_shard(name)
+        if x.dtype.is_floating_point and x.element_size() < 4:
+            x = x.to(torch.float32)  # exact, and every dtype converts from it
+        x = x.to(torch.float64)
+        pivot = torch.where(torch.isfinite(x[0]), x[0], torch.zeros_like(x[0]))
+        d = x - pivot
+        off = d.mean(0)
+        m2 = ((d - off) ** 2).sum(0)
+        return torch.stack([pivot, off, m2, x.amin(0), x.amax(0)])
+
+    def column_stats(self, name: str, local: bool = False) -> ColumnStats:
+        """Per-column ``(count, mean, std, min, max)`` of variable ``name``
+        over all ranks of the store (collective, like :meth:`add`), or over
+        this rank's shard only with ``local=True`` (not collective).
+
+        Column ``c`` is flat position ``c`` of a row (of an element for a CSR
+        variable); ``count`` is the number of rows (elements). Values are
+        taken as float64 (int64 rounds to nearest), sums are accumulated in
+        float64 around a per-column pivot taken from the data, so a mean that
+        is large against the spread costs no accuracy; ``std`` divides by
+        ``count``. ``min``/``max`` are exact. A column of equal values has
+        ``std == 0.0`` exactly. A NaN anywhere in a column makes all four of
+        its statistics NaN; ``count == 0`` makes everything NaN. Two calls on
+        unchanged data return identical bits.
+
+        On the GPU each rank reduces its shard with two kernels on the current
+        stream (transient memory independent of the number of rows) and reads
+        ``4 * disp`` numbers back with one sync; the ranks' partials are merged
+        on the host. The gather counters of :meth:`query` are not touched."""
+        meta = self._meta(name)
+        disp = meta["disp"]
+        q = self._backend.query(name)
+        n = int(q["nelems_local"] if meta["is_csr"] else q["nrows_local"])
+        if self.mode == "hip":
+            part = self._backend.column_stats(name)
+        else:
+            part = self._column_stats_host(name, n, disp)
+        if local or self.size == 1:
+            parts = [(n, part.numpy())]
+        else:
+            parts = self.comm.allgather((n, part.numpy()))
+        # Chan's merge of (count, mean, M2), in rank order; an empty shard
+        # contributes nothing. A mean is the pair pivot + offset: the pivots
+        # are values of the data, so their difference is (nearly) exact, and
+        # the difference of two means does not carry the rounding of a large
+        # mean into M2. The merged mean keeps the first shard's pivot.
+        count = 0
+        piv = off = m2 = mn = mx = torch.full((disp,), float("nan"), dtype=torch.float64)
+        for k, p in parts:
+            if k == 0:
+                continue
+            pp, po, pm2, pmn, pmx = torch.from_numpy(np.asarray(p))
+            if count == 0:
+                count, piv, off, m2, mn, mx = k, pp, po, pm2, pmn, pmx
+                continue
+            tot = count + k
+            delta = (pp - piv) + (po - off)
+            off = off + delta * (k / tot)
+            m2 = m2 + pm2 + delta * delta * (count * k / tot)
+            mn, mx = torch.minimum(mn, pmn), torch.maximum(mx, pmx)  # NaN stays
+            count = tot
+        mean = piv + off
+        std = torch.sqrt(m2 / count) if count else m2
+        flat = mn == mx  # equal values: exact, whatever the arithmetic gave
+        mean = torch.where(flat, mn, mean)
+        std = torch.where(flat, torch.zeros_like(std), std)
+        nan = torch.isnan(mn) | torch.isnan(mx)
+        nanv = torch.full_like(mean, float("nan"))
+        return ColumnStats(count, *(torch.where(nan, nanv, t).clone()
+                                    for t in (mean, std, mn, mx)))
 
     # ------------------------------------------------------------------ epochs
     def epoch_begin(self) -> None:
