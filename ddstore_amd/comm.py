@@ -34,6 +34,11 @@ _group_cache: dict = {}
 class Comm:
     """Collective metadata plane over torch.distributed (or a no-op self comm)."""
 
+    # True only on a communicator whose ranks are threads of ONE process and
+    # which says so itself (see _MpiWrap): the GPU store then exchanges plain
+    # device pointers instead of IPC handles. Never inferred.
+    same_process = False
+
     def __init__(self, group: Optional[object] = None):
         if _dist_ready():
             self._group = group  # None => WORLD
@@ -222,6 +227,9 @@ class _MpiWrap(Comm):
         self._size = mpi_comm.Get_size()
         self._group = None
         self._global_ranks = list(range(self._size))
+        # opt-in of the wrapped object, carried over; equal pids prove nothing
+        # (ranks in different pid namespaces can share a pid number)
+        self.same_process = getattr(mpi_comm, "same_process", False) is True
 
     def barrier(self) -> None:
         self._mpi.Barrier()

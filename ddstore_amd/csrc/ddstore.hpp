@@ -484,8 +484,39 @@ public:
         return py::bytes(reinterpret_cast<const char*>(&h), sizeof(h));
     }
 
+    // Address of the local shard's allocation (an empty shard has one too):
+    // what a same-process peer entry carries.
+    uint64_t base_ptr(const std::string& name) {
+        return (uint64_t)(uintptr_t)var(name).base;
+    }
+
+    // A same-process peer entry is exactly kLocalPeerBytes long: int64 pid,
+    // uint64 device pointer, both in host byte order. It is valid only inside
+    // the process that wrote it (a process cannot open an IPC handle it
+    // created itself); any other pid raises. Returns the pointer.
+    static constexpr size_t kLocalPeerBytes = 16;
+    static_assert(sizeof(hipIpcMemHandle_t) != kLocalPeerBytes,
+                  "a same-process peer entry must not be mistaken for an IPC handle");
+    static uint64_t decode_local_peer(const std::string& entry) {
+        TORCH_CHECK(entry.size() == kLocalPeerBytes,
+                    "ddstore open_peers: a same-process peer entry has ",
+                    kLocalPeerBytes, " bytes, got ", entry.size());
+        int64_t pid = 0;
+        uint64_t ptr = 0;
+        std::memcpy(&pid, entry.data(), 8);
+        std::memcpy(&ptr, entry.data() + 8, 8);
+        TORCH_CHECK(pid == (int64_t)getpid(),
+                    "ddstore open_peers: same-process peer entry written by pid ", pid,
+                    ", this is pid ", (int64_t)getpid(),
+                    " -- ranks in other processes must exchange IPC handles");
+        TORCH_CHECK(ptr != 0, "ddstore open_peers: same-process peer entry without a pointer");
+        return ptr;
+    }
+
     // Finalize a variable: map peer shards (empty bytes => use own base) and
-    // mirror the directory + pointer table to device memory.
+    // mirror the directory + pointer table to device memory. A peer's entry
+    // is an IPC handle, or a same-process entry (decode_local_peer) whose
+    // pointer is used as it is and never closed.
     // (reference analog: the MPI_Win_create collective, ddstore.hpp:56-62, or
     // the libfabric handshake's 3x Allgather, common.cxx:285-302)
     void open_peers(const std::string& name, const std::vector<std::string>& handles) {
@@ -496,6 +527,8 @@ public:
         for (int r = 0; r < nparts_; ++r) {
             if (r == rank_) {
                 v.peers[r] = v.base;
+            } else if (handles[r].size() == kLocalPeerBytes) {
+                v.peers[r] = (void*)(uintptr_t)decode_local_peer(handles[r]);
             } else {
                 TORCH_CHECK(handles[r].size() == sizeof(hipIpcMemHandle_t),
                             "ddstore open_peers: bad handle bytes for rank ", r);
@@ -942,8 +975,10 @@ public:
         TORCH_CHECK(lens.scalar_type() == at::kLong && lens.is_contiguous() &&
                         lens.device().is_cuda() && lens.numel() == idx.numel(),
                     "ddstore csr_lens: bad lens tensor");
+        // the lengths only: a bad index gets 0 here and is counted once, by
+        // the gather_csr that follows (counting here too doubled oob_skipped)
         ddstore::csr_lens(stream(), v.d_goff, idx.data_ptr<int64_t>(), idx.numel(),
-                          v.prefix[nparts_], lens.data_ptr<int64_t>(), v.d_oob,
+                          v.prefix[nparts_], lens.data_ptr<int64_t>(), nullptr,
                           nullptr);
     }
 

@@ -44,6 +44,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("add_csr", &DeviceStore::add_csr, py::call_guard<py::gil_scoped_release>())
         .def("init_csr", &DeviceStore::init_csr, py::call_guard<py::gil_scoped_release>())
         .def("ipc_handle", &DeviceStore::ipc_handle)
+        .def("base_ptr", &DeviceStore::base_ptr)
+        .def_static("decode_local_peer",
+                    [](const py::bytes& entry) {
+                        return DeviceStore::decode_local_peer(std::string(entry));
+                    })
         .def("open_peers", &DeviceStore::open_peers)
         .def("update", &DeviceStore::update, py::call_guard<py::gil_scoped_release>())
         .def("update_elems", &DeviceStore::update_elems, py::call_guard<py::gil_scoped_release>())

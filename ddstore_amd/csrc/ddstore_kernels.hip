@@ -541,7 +541,7 @@ k_csr_lens(const int64_t* goff, const int64_t* idx, int64_t nidx, int64_t nsampl
         const int64_t g = idx[i];
         if (g < 0 || g >= nsamples) {
             lens[i] = 0;
-            atomicAdd(oob, 1ull);
+            if (oob) atomicAdd(oob, 1ull);  // null: the gather behind counts it
             continue;
         }
         const int64_t L = goff[g + 1] - goff[g];
@@ -811,6 +811,10 @@ k_csr_plan2(int64_t* __restrict__ aggs, int64_t ntiles,
 // a skipped one -- and the gather reads no slot at or beyond that bound. A
 // kept sample's slots always lie below desc_cap (sum of ceil(L / item_elems)
 // over samples that fit cap_elems <= cap_elems / item_elems + nidx).
+static_assert(DDS_MAX_PARTS <= 128,
+              "the owner travels as p << 56 in a signed 64-bit descriptor and comes "
+              "back as (int)(d0 >> 56): 127 is the largest owner that keeps it "
+              "non-negative");
 __global__ void __launch_bounds__(kBlock)
 k_csr_plan3(const int64_t* __restrict__ lens_tmp,
             const int64_t* __restrict__ e0_tmp, int64_t nidx,

@@ -25,6 +25,7 @@ ddstore.hpp:251) but both values use the native path.
 from __future__ import annotations
 
 import os
+import struct
 import uuid
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -236,7 +237,13 @@ class DDStore:
 
     def _exchange_and_open(self, name: str) -> None:
         if self.mode == "hip":
-            h = self._backend.ipc_handle(name) if self.size > 1 else b""
+            if self.size > 1 and getattr(self.comm, "same_process", False) is True:
+                # ranks are threads of this process (the comm says so): a
+                # process cannot open its own IPC handle, so the entry is
+                # (pid, device pointer); the backend refuses a foreign pid
+                h = struct.pack("=qQ", os.getpid(), self._backend.base_ptr(name))
+            else:
+                h = self._backend.ipc_handle(name) if self.size > 1 else b""
             handles = self.comm.allgather(h)
             self._backend.open_peers(name, handles)
         else:
@@ -532,6 +539,9 @@ class DDStore:
             lens = torch.empty(idx.numel(), dtype=torch.int64, device=self.device)
             self._backend.csr_lens(name, idx, lens)
         else:
+            # the host backend refuses a bad index, as its get_batch does
+            if idx.numel() and not bool(((idx >= 0) & (idx < meta["nrows_total"])).all()):
+                raise IndexError("ddstore get_csr: index out of range")
             goff = meta["goff"]
             lens = goff[idx + 1] - goff[idx]
         torch.cumsum(lens, 0, out=out_off[1:])
