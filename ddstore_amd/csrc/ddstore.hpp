@@ -56,8 +56,8 @@ struct RoctxRange {
                     hipGetErrorString(_e), " at " #expr);                      \
     } while (0)
 
-inline int dds_type_of(const at::Tensor& t) {
-    switch (t.scalar_type()) {
+inline int dds_type_of(at::ScalarType st) {
+    switch (st) {
         case at::kByte: return DDS_U8;
         case at::kBool: return DDS_U8;  // stored/moved as u8 (0/1), NumPy layout
         case at::kInt: return DDS_I32;
@@ -69,18 +69,10 @@ inline int dds_type_of(const at::Tensor& t) {
         case at::kFloat8_e4m3fn: return DDS_F8E4M3;  // OCP fn, matches gfx950
         case at::kFloat8_e5m2: return DDS_F8E5M2;
         default:
-            TORCH_CHECK(false, "ddstore: unsupported dtype ", t.scalar_type());
+            TORCH_CHECK(false, "ddstore: unsupported dtype ", st);
     }
 }
-
-inline int64_t dds_itemsize(int t) {
-    switch (t) {
-        case DDS_U8: case DDS_F8E4M3: case DDS_F8E5M2: return 1;
-        case DDS_F16: case DDS_BF16: return 2;
-        case DDS_I32: case DDS_F32: return 4;
-        default: return 8;
-    }
-}
+inline int dds_type_of(const at::Tensor& t) { return dds_type_of(t.scalar_type()); }
 
 inline std::vector<int64_t> make_prefix(const std::vector<int64_t>& counts) {
     std::vector<int64_t> prefix(counts.size() + 1, 0);
@@ -288,32 +280,165 @@ struct EpochFSM {
 };
 
 // ===========================================================================
-// DeviceStore
+// What DeviceStore and HostStore share: the per-variable record and the
+// checks that do not depend on where the shard lives
 // ===========================================================================
 
-struct DeviceVar {
-    bool active = false;
+// The CSR half of a registration.
+struct CsrShape {
+    int64_t nelems;                          // elements of the local shard
+    const std::vector<int64_t>& nelems_all;  // per rank
+    const at::Tensor& goff;                  // CPU int64 [nsamples_total + 1]
+};
+
+struct VarMeta {
     bool is_csr = false;
     int dds_t = 0;
     at::ScalarType st = at::kFloat;
     int64_t row_elems = 0;    // "disp" in reference terms
     int64_t itemsize = 0;
     int64_t nrows_local = 0;  // rows for fixed-stride; samples for CSR
+    int64_t nelems_local = 0; // CSR: elements of the local shard
     std::vector<int64_t> prefix;
+    std::vector<int64_t> elem_prefix;  // CSR
     void* base = nullptr;
     size_t base_bytes = 0;
     std::vector<void*> peers;
+    // stats
+    int64_t n_gather = 0, rows_gathered = 0, bytes_gathered = 0;
+
+    // rows of the local shard's (n, row_elems) array
+    int64_t local_count() const { return is_csr ? nelems_local : nrows_local; }
+    size_t shard_bytes() const { return (size_t)(local_count() * row_elems * itemsize); }
+    int64_t nrows_total() const { return prefix.back(); }
+    // one gather call; `bytes` stays 0 where the device counts them
+    // (DDS_CTR_ELEMS, see DeviceStore::query)
+    void count(int64_t rows, int64_t bytes = 0) {
+        n_gather += 1;
+        rows_gathered += rows;
+        bytes_gathered += bytes;
+    }
+};
+
+// Everything a registration checks and records before it allocates, in the
+// words of `op` ("add", "init", "add_csr", "init_csr"). `src` null = a shard
+// zeroed now and filled later; `csr` null = fixed-stride, else `n_local` and
+// `counts` are samples. `cpu_only`: the host store's sources live on the CPU.
+inline void describe_var(VarMeta& v, const char* op, const at::Tensor* src,
+                         at::ScalarType st, int64_t row_elems, int64_t n_local,
+                         const std::vector<int64_t>& counts, const CsrShape* csr,
+                         bool cpu_only) {
+    if (src) {
+        TORCH_CHECK(src->is_contiguous() && (!cpu_only || src->device().is_cpu()),
+                    "ddstore ", op,
+                    csr ? ": values must be contiguous" : ": array must be C-contiguous",
+                    cpu_only ? " on CPU" : "");
+        TORCH_CHECK(src->numel() == (csr ? csr->nelems : n_local) * row_elems,
+                    "ddstore ", op, ": shape mismatch");
+    }
+    v.is_csr = csr != nullptr;
+    v.st = st;
+    v.dds_t = dds_type_of(st);
+    v.itemsize = dds_itemsize(v.dds_t);
+    v.row_elems = row_elems;  // CSR: feature width per element
+    v.nrows_local = n_local;
+    v.prefix = make_prefix(counts);
+    if (csr) {
+        v.nelems_local = csr->nelems;
+        v.elem_prefix = make_prefix(csr->nelems_all);
+        TORCH_CHECK(csr->goff.scalar_type() == at::kLong && csr->goff.is_contiguous() &&
+                        csr->goff.device().is_cpu() &&
+                        csr->goff.numel() == v.nrows_total() + 1,
+                    "ddstore ", op, ": bad global offsets");
+    }
+}
+
+// The checks of update (`elems` false: rows of a fixed-stride variable) and
+// update_elems (true: elements of a CSR one; offsets are LOCAL, the Python
+// layer translates a sample offset via the goff directory). Returns the byte
+// offset of the fill in the local shard.
+inline int64_t check_update(const VarMeta& v, bool elems, const at::Tensor& src,
+                            int64_t offset, bool cpu_only) {
+    if (elems) {
+        TORCH_CHECK(v.is_csr, "ddstore update_elems: CSR variables only");
+    } else {
+        TORCH_CHECK(!v.is_csr, "ddstore update: not supported for CSR variables");
+    }
+    TORCH_CHECK(src.is_contiguous() && (!cpu_only || src.device().is_cpu()),
+                "ddstore update: array must be C-contiguous", cpu_only ? " on CPU" : "");
+    TORCH_CHECK(dds_itemsize(dds_type_of(src)) == v.itemsize,
+                "ddstore update: itemsize mismatch");
+    const int64_t n = src.numel() / std::max<int64_t>(v.row_elems, 1);
+    TORCH_CHECK(src.numel() == n * v.row_elems, "ddstore update: shape mismatch");
+    TORCH_CHECK(offset >= 0 && offset + n <= v.local_count(),
+                "ddstore update: out of range");
+    return offset * v.row_elems * v.itemsize;
+}
+
+// get_range, reference get semantics: dense [start, start+count) rows from
+// ONE owner; throws if the range crosses a shard boundary
+// (ddstore.hpp:197-248). The output checks, then (source, bytes) of the range
+// in the owner's shard; the caller has checked that the peers are open.
+inline void check_range_out(const VarMeta& v, const at::Tensor& out, int64_t count,
+                            bool cpu_only) {
+    TORCH_CHECK(!v.is_csr, "ddstore get: use get_csr for CSR variables");
+    TORCH_CHECK(out.is_contiguous() && (!cpu_only || out.device().is_cpu()),
+                "ddstore get: output must be C-contiguous", cpu_only ? " on CPU" : "");
+    TORCH_CHECK(dds_itemsize(dds_type_of(out)) == v.itemsize,
+                "ddstore get: itemsize mismatch");
+    TORCH_CHECK(out.numel() == count * v.row_elems, "ddstore get: shape mismatch");
+}
+inline std::pair<const char*, size_t> owned_range(const VarMeta& v, int64_t start,
+                                                  int64_t count) {
+    TORCH_CHECK(start >= 0 && start < v.nrows_total(), "Invalid start on target");
+    const int target = owner_of_host(v.prefix, start);
+    TORCH_CHECK(start + count <= v.prefix[target + 1], "Invalid count on target");
+    return {(const char*)v.peers[target] +
+                (start - v.prefix[target]) * v.row_elems * v.itemsize,
+            (size_t)count * v.row_elems * v.itemsize};
+}
+
+// The keys of query() both stores fill alike, in this order.
+inline py::dict query_layout(const VarMeta& v) {
+    py::dict d;
+    d["nrows_local"] = v.nrows_local;
+    d["nrows_total"] = v.nrows_total();
+    d["disp"] = v.row_elems;
+    d["itemsize"] = v.itemsize;
+    d["is_csr"] = v.is_csr;
+    d["prefix"] = v.prefix;
+    if (v.is_csr) {
+        d["nelems_local"] = v.nelems_local;
+        d["elem_prefix"] = v.elem_prefix;
+    }
+    d["n_gather"] = v.n_gather;
+    d["rows_gathered"] = v.rows_gathered;
+    return d;
+}
+
+// Strict mode: raise if a variable has skipped samples (cumulative counters;
+// reset via reset_counters after an intentional OOB probe).
+inline void strict_check(const std::string& name, int64_t oob, int64_t cap) {
+    TORCH_CHECK(oob == 0, "ddstore strict: variable '", name, "': ", oob,
+                " out-of-range sample indices were skipped "
+                "(DDSTORE_STRICT=1)");
+    TORCH_CHECK(cap == 0, "ddstore strict: variable '", name, "': ", cap,
+                " CSR samples skipped: output capacity buffer too "
+                "small (DDSTORE_STRICT=1)");
+}
+
+// ===========================================================================
+// DeviceStore
+// ===========================================================================
+
+struct DeviceVar : VarMeta {
     std::vector<char> opened;    // 1 where hipIpcOpenMemHandle was used
     void** d_peers = nullptr;
     int64_t* d_prefix = nullptr;
     unsigned long long* d_oob = nullptr;  // in-kernel OOB-index counter
     // CSR extras
-    std::vector<int64_t> elem_prefix;
     int64_t* d_elem_prefix = nullptr;
     int64_t* d_goff = nullptr;   // replicated global element offsets [ntotal+1]
-    int64_t nelems_local = 0;
-    // stats
-    int64_t n_gather = 0, rows_gathered = 0, bytes_gathered = 0;
 };
 
 class DeviceStore {
@@ -332,50 +457,15 @@ public:
 
     void add(const std::string& name, const at::Tensor& src, int64_t nrows,
              int64_t row_elems, std::vector<int64_t> nrows_all) {
-        check_new(name);
-        TORCH_CHECK(src.is_contiguous(), "ddstore add: array must be C-contiguous");
-        TORCH_CHECK(src.numel() == nrows * row_elems, "ddstore add: shape mismatch");
-        DeviceVar v;
-        v.st = src.scalar_type();
-        v.dds_t = dds_type_of(src);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nrows;
-        v.prefix = make_prefix(nrows_all);
-        alloc_base(v, (size_t)(nrows * row_elems * v.itemsize));
-        try {
-            ingest(v.base, src, 0);
-        } catch (...) {
-            release(v);
-            throw;
-        }
-        v.active = true;
-        vars_[name] = std::move(v);
+        register_var(name, "add", &src, src.scalar_type(), row_elems, nrows, nrows_all,
+                     nullptr);
     }
 
     void init(const std::string& name, int64_t nrows, int64_t row_elems,
               at::ScalarType st, std::vector<int64_t> nrows_all) {
         // reference: pre-allocate zeroed shard, fill later via update
         // (ddstore.hpp:110-179; README.md:107 -- no epoch required)
-        check_new(name);
-        at::Tensor proto = at::empty({0}, at::TensorOptions().dtype(st));
-        DeviceVar v;
-        v.st = st;
-        v.dds_t = dds_type_of(proto);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nrows;
-        v.prefix = make_prefix(nrows_all);
-        alloc_base(v, (size_t)(nrows * row_elems * v.itemsize));
-        try {
-            HIP_CHECK(hipMemsetAsync(v.base, 0, v.base_bytes, stream()));
-            HIP_CHECK(hipStreamSynchronize(stream()));
-        } catch (...) {
-            release(v);
-            throw;
-        }
-        v.active = true;
-        vars_[name] = std::move(v);
+        register_var(name, "init", nullptr, st, row_elems, nrows, nrows_all, nullptr);
     }
 
     void add_csr(const std::string& name, const at::Tensor& values,
@@ -386,36 +476,9 @@ public:
         // on an element-addressed store with disp=1 (HydraGNN
         // pattern); here offsets are replicated per GPU and the gather kernel
         // packs whole samples.
-        check_new(name);
-        TORCH_CHECK(values.is_contiguous(), "ddstore add_csr: values must be contiguous");
-        TORCH_CHECK(values.numel() == nelems * row_elems, "ddstore add_csr: shape mismatch");
-        DeviceVar v;
-        v.is_csr = true;
-        v.st = values.scalar_type();
-        v.dds_t = dds_type_of(values);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;     // feature width per element
-        v.nrows_local = nsamples;
-        v.nelems_local = nelems;
-        v.prefix = make_prefix(nsamples_all);
-        v.elem_prefix = make_prefix(nelems_all);
-        TORCH_CHECK(goff_cpu.scalar_type() == at::kLong && goff_cpu.is_contiguous() &&
-                        goff_cpu.device().is_cpu() &&
-                        goff_cpu.numel() == v.prefix[nparts_] + 1,
-                    "ddstore add_csr: bad global offsets");
-        alloc_base(v, (size_t)(nelems * row_elems * v.itemsize));
-        try {
-            ingest(v.base, values, 0);
-            size_t gbytes = (size_t)goff_cpu.numel() * 8;
-            HIP_CHECK(hipMalloc((void**)&v.d_goff, gbytes));
-            HIP_CHECK(hipMemcpy(v.d_goff, goff_cpu.data_ptr<int64_t>(), gbytes,
-                                hipMemcpyHostToDevice));
-        } catch (...) {
-            release(v);
-            throw;
-        }
-        v.active = true;
-        vars_[name] = std::move(v);
+        const CsrShape csr{nelems, nelems_all, goff_cpu};
+        register_var(name, "add_csr", &values, values.scalar_type(), row_elems, nsamples,
+                     nsamples_all, &csr);
     }
 
     void init_csr(const std::string& name, int64_t nsamples, int64_t nelems,
@@ -427,54 +490,18 @@ public:
         // with update_elems -- the incremental-fill pattern the reference
         // supports for fixed-stride variables (ddstore.hpp:110-195,
         // README.md:107), extended to the first-class CSR layout.
-        check_new(name);
-        at::Tensor proto = at::empty({0}, at::TensorOptions().dtype(st));
-        DeviceVar v;
-        v.is_csr = true;
-        v.st = st;
-        v.dds_t = dds_type_of(proto);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nsamples;
-        v.nelems_local = nelems;
-        v.prefix = make_prefix(nsamples_all);
-        v.elem_prefix = make_prefix(nelems_all);
-        TORCH_CHECK(goff_cpu.scalar_type() == at::kLong && goff_cpu.is_contiguous() &&
-                        goff_cpu.device().is_cpu() &&
-                        goff_cpu.numel() == v.prefix[nparts_] + 1,
-                    "ddstore init_csr: bad global offsets");
-        alloc_base(v, (size_t)(nelems * row_elems * v.itemsize));
-        try {
-            HIP_CHECK(hipMemsetAsync(v.base, 0, v.base_bytes, stream()));
-            HIP_CHECK(hipStreamSynchronize(stream()));
-            size_t gbytes = (size_t)goff_cpu.numel() * 8;
-            HIP_CHECK(hipMalloc((void**)&v.d_goff, gbytes));
-            HIP_CHECK(hipMemcpy(v.d_goff, goff_cpu.data_ptr<int64_t>(), gbytes,
-                                hipMemcpyHostToDevice));
-        } catch (...) {
-            release(v);
-            throw;
-        }
-        v.active = true;
-        vars_[name] = std::move(v);
+        const CsrShape csr{nelems, nelems_all, goff_cpu};
+        register_var(name, "init_csr", nullptr, st, row_elems, nsamples, nsamples_all,
+                     &csr);
     }
 
+    // purely local fills (reference ddstore.hpp:181-195), see check_update
+    void update(const std::string& name, const at::Tensor& src, int64_t offset) {
+        fill(name, src, offset, false);
+    }
     void update_elems(const std::string& name, const at::Tensor& src,
                       int64_t elem_offset) {
-        // purely local CSR fill: elements [elem_offset, elem_offset+k) of
-        // this rank's shard (element offsets are LOCAL; the Python layer
-        // translates a sample offset via the goff directory)
-        DeviceVar& v = var(name);
-        TORCH_CHECK(v.is_csr, "ddstore update_elems: CSR variables only");
-        TORCH_CHECK(src.is_contiguous(), "ddstore update: array must be C-contiguous");
-        TORCH_CHECK(dds_itemsize(dds_type_of(src)) == v.itemsize,
-                    "ddstore update: itemsize mismatch");
-        int64_t nelems = src.numel() / std::max<int64_t>(v.row_elems, 1);
-        TORCH_CHECK(src.numel() == nelems * v.row_elems,
-                    "ddstore update: shape mismatch");
-        TORCH_CHECK(elem_offset >= 0 && elem_offset + nelems <= v.nelems_local,
-                    "ddstore update: out of range");
-        ingest(v.base, src, elem_offset * v.row_elems * v.itemsize);
+        fill(name, src, elem_offset, true);
     }
 
     py::bytes ipc_handle(const std::string& name) {
@@ -565,39 +592,12 @@ public:
         HIP_CHECK(hipMemset(v.d_oob, 0, DDS_NCTR * 8));
     }
 
-    void update(const std::string& name, const at::Tensor& src, int64_t offset) {
-        // purely local fill at row offset (reference ddstore.hpp:181-195)
-        DeviceVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore update: not supported for CSR variables");
-        TORCH_CHECK(src.is_contiguous(), "ddstore update: array must be C-contiguous");
-        TORCH_CHECK(dds_itemsize(dds_type_of(src)) == v.itemsize,
-                    "ddstore update: itemsize mismatch");
-        int64_t nrows = src.numel() / v.row_elems;
-        TORCH_CHECK(src.numel() == nrows * v.row_elems, "ddstore update: shape mismatch");
-        TORCH_CHECK(offset >= 0 && offset + nrows <= v.nrows_local,
-                    "ddstore update: out of range");
-        ingest(v.base, src, offset * v.row_elems * v.itemsize);
-    }
-
     void get_range(const std::string& name, int64_t start, int64_t count,
                    at::Tensor out) {
-        // reference get semantics: dense [start, start+count) rows from ONE
-        // owner; throws if the range crosses a shard boundary
-        // (ddstore.hpp:197-248)
         DeviceVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore get: use get_csr for CSR variables");
-        TORCH_CHECK(out.is_contiguous(), "ddstore get: output must be C-contiguous");
-        TORCH_CHECK(dds_itemsize(dds_type_of(out)) == v.itemsize,
-                    "ddstore get: itemsize mismatch");
-        TORCH_CHECK(out.numel() == count * v.row_elems, "ddstore get: shape mismatch");
+        check_range_out(v, out, count, false);
         check_peers(v);
-        int64_t ntotal = v.prefix[nparts_];
-        TORCH_CHECK(start >= 0 && start < ntotal, "Invalid start on target");
-        int target = owner_of_host(v.prefix, start);
-        TORCH_CHECK(start + count <= v.prefix[target + 1], "Invalid count on target");
-        const char* src = (const char*)v.peers[target] +
-                          (start - v.prefix[target]) * v.row_elems * v.itemsize;
-        size_t nb = (size_t)count * v.row_elems * v.itemsize;
+        const auto [src, nb] = owned_range(v, start, count);
         if (out.device().is_cpu()) {
             HIP_CHECK(hipStreamSynchronize(stream()));
             HIP_CHECK(hipMemcpy(out.data_ptr(), src, nb, hipMemcpyDeviceToHost));
@@ -606,73 +606,19 @@ public:
             HIP_CHECK(hipMemcpyAsync(out.data_ptr(), src, nb,
                                      hipMemcpyDeviceToDevice, stream()));
         }
-        v.n_gather += 1;
-        v.rows_gathered += count;
-        v.bytes_gathered += nb;
+        v.count(count, (int64_t)nb);
     }
 
     void gather(const std::string& name, const at::Tensor& idx, at::Tensor out) {
         // the batched hot path: one launch per minibatch
         RoctxRange rr_("ddstore::gather");
-        DeviceVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore gather: use gather_csr for CSR variables");
-        check_peers(v);
-        check_idx(idx);
-        int64_t nidx = idx.numel();
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        out.device().index() == device_,
-                    "ddstore gather: output must be a contiguous tensor on the store device");
-        TORCH_CHECK(out.numel() == nidx * v.row_elems, "ddstore gather: shape mismatch");
-        // byte move only for the SAME dds type (bool aliases u8); any other
-        // dtype pair converts numerically -- a same-size pair like f16->bf16
-        // must NOT silently reinterpret bits (the CPU path converts too)
-        int out_t = dds_type_of(out);
-        ddstore::gather_rows(stream(), (const void* const*)v.d_peers, v.d_prefix,
-                             (const void* const*)v.peers.data(), v.prefix.data(),
-                             nparts_, idx.data_ptr<int64_t>(), nidx, v.row_elems,
-                             v.dds_t, out_t, out.data_ptr(), v.d_oob);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        v.bytes_gathered += nidx * v.row_elems * v.itemsize;
+        gather_fixed(name, idx, out, Affine{});
     }
 
     void gather_affine(const std::string& name, const at::Tensor& idx,
                        at::Tensor out, double scale, double shift) {
         RoctxRange rr_("ddstore::gather_affine");
-        DeviceVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore gather: use gather_csr for CSR variables");
-        check_peers(v);
-        check_idx(idx);
-        int64_t nidx = idx.numel();
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        out.device().index() == device_,
-                    "ddstore gather: output must be a contiguous tensor on the store device");
-        TORCH_CHECK(out.numel() == nidx * v.row_elems, "ddstore gather: shape mismatch");
-        int out_t = dds_type_of(out);
-        TORCH_CHECK(out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
-                    "ddstore gather: affine output must be f32/f16/bf16");
-        ddstore::gather_rows_affine(stream(), (const void* const*)v.d_peers,
-                                    v.d_prefix, (const void* const*)v.peers.data(),
-                                    v.prefix.data(), nparts_, idx.data_ptr<int64_t>(),
-                                    nidx, v.row_elems, v.dds_t, out_t,
-                                    (float)scale, (float)shift, out.data_ptr(),
-                                    v.d_oob);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        v.bytes_gathered += nidx * v.row_elems * v.itemsize;
-    }
-
-    // One per-column affine vector: `n` contiguous floats on the store
-    // device, 16-B aligned (the kernels load them as vectors).
-    const float* affine_vec(const at::Tensor& t, int64_t n) const {
-        TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() &&
-                        t.device().is_cuda() && t.device().index() == device_ &&
-                        t.numel() == n,
-                    "ddstore: a per-column affine vector must be a contiguous float32 "
-                    "tensor of disp = ", n, " values on the store device");
-        TORCH_CHECK(((uintptr_t)t.data_ptr()) % 16 == 0,
-                    "ddstore: a per-column affine vector must be 16-byte aligned");
-        return t.data_ptr<float>();
+        gather_fixed(name, idx, out, Affine{true, (float)scale, (float)shift});
     }
 
     // gather_affine with one (scale, shift) pair per column.
@@ -680,28 +626,7 @@ public:
                             at::Tensor out, const at::Tensor& scale,
                             const at::Tensor& shift) {
         RoctxRange rr_("ddstore::gather_affine_cols");
-        DeviceVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore gather: use gather_csr for CSR variables");
-        check_peers(v);
-        check_idx(idx);
-        int64_t nidx = idx.numel();
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        out.device().index() == device_,
-                    "ddstore gather: output must be a contiguous tensor on the store device");
-        TORCH_CHECK(out.numel() == nidx * v.row_elems, "ddstore gather: shape mismatch");
-        int out_t = dds_type_of(out);
-        TORCH_CHECK(out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
-                    "ddstore gather: affine output must be f32/f16/bf16");
-        TORCH_CHECK(v.row_elems < (int64_t(1) << 31), "ddstore gather: row too long");
-        ddstore::gather_rows_affine_cols(
-            stream(), (const void* const*)v.d_peers, v.d_prefix,
-            (const void* const*)v.peers.data(), v.prefix.data(), nparts_,
-            idx.data_ptr<int64_t>(), nidx, v.row_elems, v.dds_t, out_t,
-            affine_vec(scale, v.row_elems), affine_vec(shift, v.row_elems),
-            out.data_ptr(), v.d_oob);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        v.bytes_gathered += nidx * v.row_elems * v.itemsize;
+        gather_fixed(name, idx, out, Affine{true}, &scale, &shift);
     }
 
     // Column statistics of the local shard (fixed-stride: rows; CSR:
@@ -713,7 +638,7 @@ public:
     at::Tensor column_stats(const std::string& name) {
         RoctxRange rr_("ddstore::column_stats");
         DeviceVar& v = var(name);
-        const int64_t n = v.is_csr ? v.nelems_local : v.nrows_local;
+        const int64_t n = v.local_count();
         const int64_t d = v.row_elems;
         if (n == 0 || d == 0)
             return at::full({5, d}, std::numeric_limits<double>::quiet_NaN(),
@@ -737,24 +662,17 @@ public:
         check_idx(out_off);
         int64_t nidx = idx.numel();
         TORCH_CHECK(out_off.numel() == nidx + 1, "ddstore gather_csr: bad out_off");
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        dds_type_of(out) == v.dds_t,
-                    "ddstore gather_csr: bad output tensor");
+        check_ragged_out(v, out);
         TORCH_CHECK(out.numel() >= total_elems * v.row_elems,
                     "ddstore gather_csr: output too small");
         // capacity passed to the kernel is the REAL buffer capacity: a sample
         // whose slice would end past it is skipped + counted, never written
         // out of bounds
         const int64_t cap = out.numel() / std::max<int64_t>(v.row_elems, 1);
-        ddstore::gather_csr(stream(), (const void* const*)v.d_peers, v.d_prefix,
-                            v.d_elem_prefix, nparts_, v.d_goff,
-                            idx.data_ptr<int64_t>(), nidx,
-                            out_off.data_ptr<int64_t>(),
-                            v.row_elems * v.itemsize, cap,
+        ddstore::gather_csr(stream(), csr_dir(v), idx.data_ptr<int64_t>(), nidx,
+                            out_off.data_ptr<int64_t>(), v.row_elems * v.itemsize, cap,
                             out.data_ptr(), v.d_oob);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        v.bytes_gathered += total_elems * v.row_elems * v.itemsize;
+        v.count(nidx, total_elems * v.row_elems * v.itemsize);
     }
 
     // One-call CSR fetch: ONE fused kernel (per-sample lens + decoupled-
@@ -831,18 +749,15 @@ public:
             auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
             at::Tensor scratch = at::empty(
                 {(int64_t)ddstore::csr_plan_scratch_bytes(nidx)}, bopts);
-            ddstore::csr_offsets(stream(), ev.d_goff, ev.prefix[nparts_],
-                                 idx.data_ptr<int64_t>(), nidx,
+            const CsrDir edir = csr_dir(ev);
+            ddstore::csr_offsets(stream(), edir, idx.data_ptr<int64_t>(), nidx,
                                  edge_ptr.data_ptr<int64_t>(), scratch.data_ptr(),
                                  ev.d_oob);
             ddstore::gather_csr_relabel(
-                stream(), (const void* const*)ev.d_peers, ev.d_prefix,
-                ev.d_elem_prefix, nparts_, ev.d_goff, idx.data_ptr<int64_t>(), nidx,
+                stream(), edir, idx.data_ptr<int64_t>(), nidx,
                 ptr.data_ptr<int64_t>(), edge_ptr.data_ptr<int64_t>(), ncap, ecap,
                 ev.dds_t, out_t, coo, edge_out.data_ptr(), ev.d_oob);
-            ev.n_gather += 1;
-            ev.rows_gathered += nidx;
-            // bytes accounted via the device DDS_CTR_ELEMS counter (see query)
+            ev.count(nidx);
         }
         ddstore::graph_fill(stream(), ptr.data_ptr<int64_t>(),
                             edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, out_t,
@@ -851,43 +766,6 @@ public:
         return {ptr, edge_ptr};
     }
 
-private:
-    // body of gather_csr_fast, shared with gather_graph; `v` and `idx` are
-    // checked by the caller
-    at::Tensor csr_fast(DeviceVar& v, const at::Tensor& idx, at::Tensor out) {
-        const int64_t nidx = idx.numel();
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        dds_type_of(out) == v.dds_t,
-                    "ddstore gather_csr: bad output tensor");
-        auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
-        at::Tensor off = at::empty({nidx + 1}, opts);
-        if (nidx == 0) {
-            off.zero_();
-            return off;
-        }
-        const int64_t cap = out.numel() / std::max<int64_t>(v.row_elems, 1);
-        const int64_t elem_bytes = v.row_elems * v.itemsize;
-        auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
-        at::Tensor scratch = at::empty(
-            {(int64_t)ddstore::csr_plan_scratch_bytes(nidx)}, bopts);
-        const int64_t desc_cap =
-            cap / ddstore::csr_item_elems(elem_bytes) + nidx;
-        // 2 i64 per item; uninitialised on purpose: the gather only acts on
-        // slots the plan wrote in this call (see gather_csr_balanced)
-        at::Tensor desc = at::empty({2 * desc_cap}, opts);
-        ddstore::gather_csr_balanced(
-            stream(), (const void* const*)v.d_peers, v.d_prefix,
-            v.d_elem_prefix, nparts_, v.d_goff, v.prefix[nparts_],
-            idx.data_ptr<int64_t>(), nidx, elem_bytes, cap,
-            off.data_ptr<int64_t>(), out.data_ptr(), v.d_oob,
-            scratch.data_ptr(), desc.data_ptr<int64_t>(), desc_cap);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        // bytes accounted via the device DDS_CTR_ELEMS counter (see query)
-        return off;
-    }
-
-public:
     // Padded CSR fetch: one launch writes the dense (n, max_len, disp)
     // batch (cast / affine fused, pad broadcast from `pad_bits`, the raw
     // bits of one output element) and the true per-sample lengths. The
@@ -899,34 +777,8 @@ public:
                            int64_t pad_bits, bool affine, double scale,
                            double shift) {
         RoctxRange rr_("ddstore::gather_csr_padded");
-        DeviceVar& v = var(name);
-        TORCH_CHECK(v.is_csr, "ddstore gather_csr_padded: not a CSR variable");
-        check_peers(v);
-        check_idx(idx);
-        const int64_t nidx = idx.numel();
-        TORCH_CHECK(max_len >= 1, "ddstore gather_csr_padded: max_len must be >= 1");
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        out.device().index() == device_,
-                    "ddstore gather_csr_padded: output must be a contiguous tensor "
-                    "on the store device");
-        TORCH_CHECK(out.numel() == nidx * max_len * v.row_elems,
-                    "ddstore gather_csr_padded: shape mismatch");
-        TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.is_contiguous() &&
-                        lengths.device().is_cuda() &&
-                        lengths.device().index() == device_ &&
-                        lengths.numel() == nidx,
-                    "ddstore gather_csr_padded: bad lengths tensor");
-        const int out_t = dds_type_of(out);
-        TORCH_CHECK(!affine || out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
-                    "ddstore gather_csr_padded: affine output must be f32/f16/bf16");
-        ddstore::gather_csr_padded(
-            stream(), (const void* const*)v.d_peers, v.d_prefix, v.d_elem_prefix,
-            nparts_, v.d_goff, v.prefix[nparts_], idx.data_ptr<int64_t>(), nidx,
-            v.row_elems, max_len, v.dds_t, out_t, affine, (float)scale, (float)shift,
-            (uint64_t)pad_bits, out.data_ptr(), lengths.data_ptr<int64_t>(), v.d_oob);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        // bytes accounted via the device DDS_CTR_ELEMS counter (see query)
+        padded(name, idx, out, lengths, max_len, pad_bits,
+               Affine{affine, (float)scale, (float)shift});
     }
 
     // gather_csr_padded with one (scale, shift) pair per column of an element.
@@ -935,36 +787,7 @@ public:
                                 int64_t pad_bits, const at::Tensor& scale,
                                 const at::Tensor& shift) {
         RoctxRange rr_("ddstore::gather_csr_padded_cols");
-        DeviceVar& v = var(name);
-        TORCH_CHECK(v.is_csr, "ddstore gather_csr_padded: not a CSR variable");
-        check_peers(v);
-        check_idx(idx);
-        const int64_t nidx = idx.numel();
-        TORCH_CHECK(max_len >= 1, "ddstore gather_csr_padded: max_len must be >= 1");
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
-                        out.device().index() == device_,
-                    "ddstore gather_csr_padded: output must be a contiguous tensor "
-                    "on the store device");
-        TORCH_CHECK(out.numel() == nidx * max_len * v.row_elems,
-                    "ddstore gather_csr_padded: shape mismatch");
-        TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.is_contiguous() &&
-                        lengths.device().is_cuda() &&
-                        lengths.device().index() == device_ &&
-                        lengths.numel() == nidx,
-                    "ddstore gather_csr_padded: bad lengths tensor");
-        const int out_t = dds_type_of(out);
-        TORCH_CHECK(out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16,
-                    "ddstore gather_csr_padded: affine output must be f32/f16/bf16");
-        TORCH_CHECK(v.row_elems >= 1 && v.row_elems < (int64_t(1) << 31) / 16,
-                    "ddstore gather_csr_padded: bad element width for a column affine");
-        ddstore::gather_csr_padded_cols(
-            stream(), (const void* const*)v.d_peers, v.d_prefix, v.d_elem_prefix,
-            nparts_, v.d_goff, v.prefix[nparts_], idx.data_ptr<int64_t>(), nidx,
-            v.row_elems, max_len, v.dds_t, out_t, affine_vec(scale, v.row_elems),
-            affine_vec(shift, v.row_elems), (uint64_t)pad_bits, out.data_ptr(),
-            lengths.data_ptr<int64_t>(), v.d_oob);
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
+        padded(name, idx, out, lengths, max_len, pad_bits, Affine{true}, &scale, &shift);
     }
 
     void csr_lens(const std::string& name, const at::Tensor& idx, at::Tensor lens) {
@@ -977,9 +800,8 @@ public:
                     "ddstore csr_lens: bad lens tensor");
         // the lengths only: a bad index gets 0 here and is counted once, by
         // the gather_csr that follows (counting here too doubled oob_skipped)
-        ddstore::csr_lens(stream(), v.d_goff, idx.data_ptr<int64_t>(), idx.numel(),
-                          v.prefix[nparts_], lens.data_ptr<int64_t>(), nullptr,
-                          nullptr);
+        ddstore::csr_lens(stream(), csr_dir(v), idx.data_ptr<int64_t>(), idx.numel(),
+                          lens.data_ptr<int64_t>(), nullptr, nullptr);
     }
 
     void scatter_local(const std::string& name, const at::Tensor& local_idx,
@@ -1002,9 +824,8 @@ public:
     // Zero-copy view of the local shard as a torch tensor (does NOT own).
     at::Tensor local_shard(const std::string& name) {
         DeviceVar& v = var(name);
-        int64_t n = v.is_csr ? v.nelems_local : v.nrows_local;
         auto opts = at::TensorOptions().dtype(v.st).device(at::kCUDA, device_);
-        return at::from_blob(v.base, {n, v.row_elems}, opts);
+        return at::from_blob(v.base, {v.local_count(), v.row_elems}, opts);
     }
 
     void epoch_begin() {
@@ -1018,8 +839,6 @@ public:
     }
     bool epoch_active() const { return fsm_.fence_active; }
 
-    // Raise if any variable has skipped samples (cumulative counters; reset
-    // via reset_counters after an intentional OOB probe).
     void check_strict() {
         for (auto& kv : vars_) {
             DeviceVar& v = kv.second;
@@ -1027,32 +846,13 @@ public:
             unsigned long long ctrs[DDS_NCTR] = {0, 0, 0};
             HIP_CHECK(hipMemcpy(ctrs, v.d_oob, DDS_NCTR * 8,
                                 hipMemcpyDeviceToHost));
-            TORCH_CHECK(ctrs[DDS_CTR_OOB] == 0, "ddstore strict: variable '",
-                        kv.first, "': ", ctrs[DDS_CTR_OOB],
-                        " out-of-range sample indices were skipped "
-                        "(DDSTORE_STRICT=1)");
-            TORCH_CHECK(ctrs[DDS_CTR_CAP] == 0, "ddstore strict: variable '",
-                        kv.first, "': ", ctrs[DDS_CTR_CAP],
-                        " CSR samples skipped: output capacity buffer too "
-                        "small (DDSTORE_STRICT=1)");
+            strict_check(kv.first, (int64_t)ctrs[DDS_CTR_OOB], (int64_t)ctrs[DDS_CTR_CAP]);
         }
     }
 
     py::dict query(const std::string& name) {
         DeviceVar& v = var(name);
-        py::dict d;
-        d["nrows_local"] = v.nrows_local;
-        d["nrows_total"] = v.prefix[nparts_];
-        d["disp"] = v.row_elems;
-        d["itemsize"] = v.itemsize;
-        d["is_csr"] = v.is_csr;
-        d["prefix"] = v.prefix;
-        if (v.is_csr) {
-            d["nelems_local"] = v.nelems_local;
-            d["elem_prefix"] = v.elem_prefix;
-        }
-        d["n_gather"] = v.n_gather;
-        d["rows_gathered"] = v.rows_gathered;
+        py::dict d = query_layout(v);
         int64_t bytes = v.bytes_gathered;
         if (v.d_oob) {
             unsigned long long ctrs[DDS_NCTR] = {0, 0, 0};
@@ -1139,18 +939,186 @@ private:
     }
 
     void release(DeviceVar& v) {
-        if (!v.active && !v.base) return;
+        if (!v.base) return;
         for (int r = 0; r < (int)v.peers.size(); ++r)
             if (v.opened.size() > (size_t)r && v.opened[r] && v.peers[r])
                 (void)hipIpcCloseMemHandle(v.peers[r]);
         v.peers.clear();
         if (v.d_peers) (void)hipFree(v.d_peers);
         if (v.d_goff) (void)hipFree(v.d_goff);
-        if (v.base) (void)hipFree(v.base);
+        (void)hipFree(v.base);
         v.base = nullptr;
         v.d_peers = nullptr;
         v.d_goff = nullptr;
-        v.active = false;
+    }
+
+    // The one registration body (arguments as describe_var): allocate, fill
+    // from `src` or with zeros, upload the CSR offsets, release on any throw.
+    void register_var(const std::string& name, const char* op, const at::Tensor* src,
+                      at::ScalarType st, int64_t row_elems, int64_t n_local,
+                      const std::vector<int64_t>& counts, const CsrShape* csr) {
+        check_new(name);
+        DeviceVar v;
+        describe_var(v, op, src, st, row_elems, n_local, counts, csr, false);
+        alloc_base(v, v.shard_bytes());
+        try {
+            if (src) {
+                ingest(v.base, *src, 0);
+            } else {
+                HIP_CHECK(hipMemsetAsync(v.base, 0, v.base_bytes, stream()));
+                HIP_CHECK(hipStreamSynchronize(stream()));
+            }
+            if (csr) {
+                size_t gbytes = (size_t)csr->goff.numel() * 8;
+                HIP_CHECK(hipMalloc((void**)&v.d_goff, gbytes));
+                HIP_CHECK(hipMemcpy(v.d_goff, csr->goff.data_ptr<int64_t>(), gbytes,
+                                    hipMemcpyHostToDevice));
+            }
+        } catch (...) {
+            release(v);
+            throw;
+        }
+        vars_[name] = std::move(v);
+    }
+
+    // body of update and update_elems
+    void fill(const std::string& name, const at::Tensor& src, int64_t offset, bool elems) {
+        DeviceVar& v = var(name);
+        ingest(v.base, src, check_update(v, elems, src, offset, false));
+    }
+
+    // The only places that spell a variable's directory for the launchers
+    // (void** converts to const void* const* without a cast).
+    RowDir row_dir(const DeviceVar& v) const {
+        return {v.d_peers, v.d_prefix, v.peers.data(), v.prefix.data(), nparts_};
+    }
+    CsrDir csr_dir(const DeviceVar& v) const {
+        return {v.d_peers, v.d_prefix, v.d_elem_prefix, nparts_, v.d_goff,
+                v.nrows_total()};
+    }
+
+    // The output check of a gather, in the caller's words: contiguous and on
+    // the store device.
+    void check_out(const at::Tensor& out, const char* msg) const {
+        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
+                        out.device().index() == device_, msg);
+    }
+    // The ragged CSR forms ask for any GPU and the store dtype instead.
+    static void check_ragged_out(const DeviceVar& v, const at::Tensor& out) {
+        TORCH_CHECK(out.is_contiguous() && out.device().is_cuda() &&
+                        dds_type_of(out) == v.dds_t,
+                    "ddstore gather_csr: bad output tensor");
+    }
+
+    // One per-column affine vector: `n` contiguous floats on the store
+    // device, 16-B aligned (the kernels load them as vectors).
+    const float* affine_vec(const at::Tensor& t, int64_t n) const {
+        TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                        t.device().is_cuda() && t.device().index() == device_ &&
+                        t.numel() == n,
+                    "ddstore: a per-column affine vector must be a contiguous float32 "
+                    "tensor of disp = ", n, " values on the store device");
+        TORCH_CHECK(((uintptr_t)t.data_ptr()) % 16 == 0,
+                    "ddstore: a per-column affine vector must be 16-byte aligned");
+        return t.data_ptr<float>();
+    }
+    static bool float_out(int out_t) {
+        return out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16;
+    }
+
+    // The fixed-stride gather body: gather (xf off), gather_affine (the
+    // scalar pair in xf) and gather_affine_cols (`scale` / `shift` given: one
+    // pair per column, which also limits the row width).
+    void gather_fixed(const std::string& name, const at::Tensor& idx, at::Tensor& out,
+                      Affine xf, const at::Tensor* scale = nullptr,
+                      const at::Tensor* shift = nullptr) {
+        DeviceVar& v = var(name);
+        TORCH_CHECK(!v.is_csr, "ddstore gather: use gather_csr for CSR variables");
+        check_peers(v);
+        check_idx(idx);
+        const int64_t nidx = idx.numel();
+        check_out(out, "ddstore gather: output must be a contiguous tensor on the store "
+                       "device");
+        TORCH_CHECK(out.numel() == nidx * v.row_elems, "ddstore gather: shape mismatch");
+        // byte move only for the SAME dds type (bool aliases u8); any other
+        // dtype pair converts numerically -- a same-size pair like f16->bf16
+        // must NOT silently reinterpret bits (the CPU path converts too)
+        const int out_t = dds_type_of(out);
+        TORCH_CHECK(!xf.on || float_out(out_t),
+                    "ddstore gather: affine output must be f32/f16/bf16");
+        if (scale) {
+            TORCH_CHECK(v.row_elems < (int64_t(1) << 31), "ddstore gather: row too long");
+            xf.d_scale = affine_vec(*scale, v.row_elems);
+            xf.d_shift = affine_vec(*shift, v.row_elems);
+        }
+        ddstore::gather_rows(stream(), row_dir(v), idx.data_ptr<int64_t>(), nidx,
+                             v.row_elems, v.dds_t, out_t, xf, out.data_ptr(), v.d_oob);
+        v.count(nidx, nidx * v.row_elems * v.itemsize);
+    }
+
+    // The padded CSR gather body, `xf`, `scale` and `shift` as for
+    // gather_fixed. Bytes are counted on the device (DDS_CTR_ELEMS, see query).
+    void padded(const std::string& name, const at::Tensor& idx, at::Tensor& out,
+                at::Tensor& lengths, int64_t max_len, int64_t pad_bits, Affine xf,
+                const at::Tensor* scale = nullptr, const at::Tensor* shift = nullptr) {
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.is_csr, "ddstore gather_csr_padded: not a CSR variable");
+        check_peers(v);
+        check_idx(idx);
+        const int64_t nidx = idx.numel();
+        TORCH_CHECK(max_len >= 1, "ddstore gather_csr_padded: max_len must be >= 1");
+        check_out(out, "ddstore gather_csr_padded: output must be a contiguous tensor "
+                       "on the store device");
+        TORCH_CHECK(out.numel() == nidx * max_len * v.row_elems,
+                    "ddstore gather_csr_padded: shape mismatch");
+        TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.is_contiguous() &&
+                        lengths.device().is_cuda() &&
+                        lengths.device().index() == device_ &&
+                        lengths.numel() == nidx,
+                    "ddstore gather_csr_padded: bad lengths tensor");
+        const int out_t = dds_type_of(out);
+        TORCH_CHECK(!xf.on || float_out(out_t),
+                    "ddstore gather_csr_padded: affine output must be f32/f16/bf16");
+        if (scale) {
+            TORCH_CHECK(v.row_elems >= 1 && v.row_elems < (int64_t(1) << 31) / 16,
+                        "ddstore gather_csr_padded: bad element width for a column affine");
+            xf.d_scale = affine_vec(*scale, v.row_elems);
+            xf.d_shift = affine_vec(*shift, v.row_elems);
+        }
+        ddstore::gather_csr_padded(
+            stream(), csr_dir(v), idx.data_ptr<int64_t>(), nidx, v.row_elems, max_len,
+            v.dds_t, out_t, xf, (uint64_t)pad_bits, out.data_ptr(),
+            lengths.data_ptr<int64_t>(), v.d_oob);
+        v.count(nidx);
+    }
+
+    // body of gather_csr_fast, shared with gather_graph; `v` and `idx` are
+    // checked by the caller. Bytes are counted on the device, as in `padded`.
+    at::Tensor csr_fast(DeviceVar& v, const at::Tensor& idx, at::Tensor out) {
+        const int64_t nidx = idx.numel();
+        check_ragged_out(v, out);
+        auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
+        at::Tensor off = at::empty({nidx + 1}, opts);
+        if (nidx == 0) {
+            off.zero_();
+            return off;
+        }
+        const int64_t cap = out.numel() / std::max<int64_t>(v.row_elems, 1);
+        const int64_t elem_bytes = v.row_elems * v.itemsize;
+        auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
+        at::Tensor scratch = at::empty(
+            {(int64_t)ddstore::csr_plan_scratch_bytes(nidx)}, bopts);
+        const int64_t desc_cap =
+            cap / ddstore::csr_item_elems(elem_bytes) + nidx;
+        // 2 i64 per item; uninitialised on purpose: the gather only acts on
+        // slots the plan wrote in this call (see gather_csr_balanced)
+        at::Tensor desc = at::empty({2 * desc_cap}, opts);
+        ddstore::gather_csr_balanced(
+            stream(), csr_dir(v), idx.data_ptr<int64_t>(), nidx, elem_bytes, cap,
+            off.data_ptr<int64_t>(), out.data_ptr(), v.d_oob,
+            scratch.data_ptr(), desc.data_ptr<int64_t>(), desc_cap);
+        v.count(nidx);
+        return off;
     }
 
     int device_;
@@ -1164,26 +1132,12 @@ private:
 // HostStore (POSIX shm, CPU compatibility path -- BASELINE config 1)
 // ===========================================================================
 
-struct HostVar {
-    bool active = false;
-    bool is_csr = false;
+struct HostVar : VarMeta {
     bool creator = false;
-    int dds_t = 0;
-    at::ScalarType st = at::kFloat;
-    int64_t row_elems = 0;
-    int64_t itemsize = 0;
-    int64_t nrows_local = 0;
-    int64_t nelems_local = 0;
-    std::vector<int64_t> prefix;
-    std::vector<int64_t> elem_prefix;
     std::string shm_name;
-    void* base = nullptr;
-    size_t base_bytes = 0;
-    std::vector<void*> peers;
     std::vector<size_t> peer_bytes;
     std::vector<std::string> peer_names;
     at::Tensor goff;  // CPU int64 [ntotal+1], replicated
-    int64_t n_gather = 0, rows_gathered = 0, bytes_gathered = 0;
     int64_t oob_skipped = 0, cap_skipped = 0;
 };
 
@@ -1202,77 +1156,27 @@ public:
         return "/dds-" + session_ + "-" + var + "-" + std::to_string(rank_);
     }
 
+    // The four registrations, as DeviceStore's; each returns the name of the
+    // shard's shm segment.
     std::string add(const std::string& name, const at::Tensor& src, int64_t nrows,
                     int64_t row_elems, std::vector<int64_t> nrows_all) {
-        check_new(name);
-        TORCH_CHECK(src.is_contiguous() && src.device().is_cpu(),
-                    "ddstore add: array must be C-contiguous on CPU");
-        TORCH_CHECK(src.numel() == nrows * row_elems, "ddstore add: shape mismatch");
-        HostVar v;
-        v.st = src.scalar_type();
-        v.dds_t = dds_type_of(src);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nrows;
-        v.prefix = make_prefix(nrows_all);
-        create_shm(v, name, (size_t)(nrows * row_elems * v.itemsize));
-        std::memcpy(v.base, src.data_ptr(), (size_t)src.numel() * v.itemsize);
-        try_collapse_hugepages(v.base, v.base_bytes);
-        v.active = true;
-        std::string n = v.shm_name;
-        vars_[name] = std::move(v);
-        return n;
+        return register_var(name, "add", &src, src.scalar_type(), row_elems, nrows,
+                            nrows_all, nullptr);
     }
 
     std::string init(const std::string& name, int64_t nrows, int64_t row_elems,
                      at::ScalarType st, std::vector<int64_t> nrows_all) {
-        check_new(name);
-        at::Tensor proto = at::empty({0}, at::TensorOptions().dtype(st));
-        HostVar v;
-        v.st = st;
-        v.dds_t = dds_type_of(proto);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nrows;
-        v.prefix = make_prefix(nrows_all);
-        create_shm(v, name, (size_t)(nrows * row_elems * v.itemsize));
-        std::memset(v.base, 0, v.base_bytes);
-        try_collapse_hugepages(v.base, v.base_bytes);
-        v.active = true;
-        std::string n = v.shm_name;
-        vars_[name] = std::move(v);
-        return n;
+        return register_var(name, "init", nullptr, st, row_elems, nrows, nrows_all,
+                            nullptr);
     }
 
     std::string add_csr(const std::string& name, const at::Tensor& values,
                         int64_t nsamples, int64_t nelems, int64_t row_elems,
                         std::vector<int64_t> nsamples_all,
                         std::vector<int64_t> nelems_all, const at::Tensor& goff_cpu) {
-        check_new(name);
-        HostVar v;
-        v.is_csr = true;
-        v.st = values.scalar_type();
-        v.dds_t = dds_type_of(values);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nsamples;
-        v.nelems_local = nelems;
-        v.prefix = make_prefix(nsamples_all);
-        v.elem_prefix = make_prefix(nelems_all);
-        TORCH_CHECK(values.is_contiguous() && values.device().is_cpu(),
-                    "ddstore add_csr: values must be contiguous on CPU");
-        TORCH_CHECK(values.numel() == nelems * row_elems, "ddstore add_csr: shape mismatch");
-        TORCH_CHECK(goff_cpu.scalar_type() == at::kLong && goff_cpu.is_contiguous() &&
-                        goff_cpu.numel() == v.prefix[nparts_] + 1,
-                    "ddstore add_csr: bad global offsets");
-        v.goff = goff_cpu;
-        create_shm(v, name, (size_t)(nelems * row_elems * v.itemsize));
-        std::memcpy(v.base, values.data_ptr(), (size_t)values.numel() * v.itemsize);
-        try_collapse_hugepages(v.base, v.base_bytes);
-        v.active = true;
-        std::string n = v.shm_name;
-        vars_[name] = std::move(v);
-        return n;
+        const CsrShape csr{nelems, nelems_all, goff_cpu};
+        return register_var(name, "add_csr", &values, values.scalar_type(), row_elems,
+                            nsamples, nsamples_all, &csr);
     }
 
     std::string init_csr(const std::string& name, int64_t nsamples,
@@ -1280,46 +1184,17 @@ public:
                          std::vector<int64_t> nsamples_all,
                          std::vector<int64_t> nelems_all,
                          const at::Tensor& goff_cpu) {
-        check_new(name);
-        at::Tensor proto = at::empty({0}, at::TensorOptions().dtype(st));
-        HostVar v;
-        v.is_csr = true;
-        v.st = st;
-        v.dds_t = dds_type_of(proto);
-        v.itemsize = dds_itemsize(v.dds_t);
-        v.row_elems = row_elems;
-        v.nrows_local = nsamples;
-        v.nelems_local = nelems;
-        v.prefix = make_prefix(nsamples_all);
-        v.elem_prefix = make_prefix(nelems_all);
-        TORCH_CHECK(goff_cpu.scalar_type() == at::kLong && goff_cpu.is_contiguous() &&
-                        goff_cpu.numel() == v.prefix[nparts_] + 1,
-                    "ddstore init_csr: bad global offsets");
-        v.goff = goff_cpu;
-        create_shm(v, name, (size_t)(nelems * row_elems * v.itemsize));
-        std::memset(v.base, 0, v.base_bytes);
-        try_collapse_hugepages(v.base, v.base_bytes);
-        v.active = true;
-        std::string n = v.shm_name;
-        vars_[name] = std::move(v);
-        return n;
+        const CsrShape csr{nelems, nelems_all, goff_cpu};
+        return register_var(name, "init_csr", nullptr, st, row_elems, nsamples,
+                            nsamples_all, &csr);
     }
 
+    void update(const std::string& name, const at::Tensor& src, int64_t offset) {
+        fill(name, src, offset, false);
+    }
     void update_elems(const std::string& name, const at::Tensor& src,
                       int64_t elem_offset) {
-        HostVar& v = var(name);
-        TORCH_CHECK(v.is_csr, "ddstore update_elems: CSR variables only");
-        TORCH_CHECK(src.is_contiguous() && src.device().is_cpu(),
-                    "ddstore update: array must be C-contiguous on CPU");
-        TORCH_CHECK(dds_itemsize(dds_type_of(src)) == v.itemsize,
-                    "ddstore update: itemsize mismatch");
-        int64_t nelems = src.numel() / (v.row_elems > 0 ? v.row_elems : 1);
-        TORCH_CHECK(src.numel() == nelems * v.row_elems,
-                    "ddstore update: shape mismatch");
-        TORCH_CHECK(elem_offset >= 0 && elem_offset + nelems <= v.nelems_local,
-                    "ddstore update: out of range");
-        std::memcpy((char*)v.base + elem_offset * v.row_elems * v.itemsize,
-                    src.data_ptr(), (size_t)src.numel() * v.itemsize);
+        fill(name, src, elem_offset, true);
     }
 
     void open_peers(const std::string& name, const std::vector<std::string>& names) {
@@ -1352,42 +1227,14 @@ public:
         }
     }
 
-    void update(const std::string& name, const at::Tensor& src, int64_t offset) {
-        HostVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore update: not supported for CSR variables");
-        TORCH_CHECK(src.is_contiguous() && src.device().is_cpu(),
-                    "ddstore update: array must be C-contiguous on CPU");
-        TORCH_CHECK(dds_itemsize(dds_type_of(src)) == v.itemsize,
-                    "ddstore update: itemsize mismatch");
-        int64_t nrows = src.numel() / v.row_elems;
-        TORCH_CHECK(src.numel() == nrows * v.row_elems, "ddstore update: shape mismatch");
-        TORCH_CHECK(offset >= 0 && offset + nrows <= v.nrows_local,
-                    "ddstore update: out of range");
-        std::memcpy((char*)v.base + offset * v.row_elems * v.itemsize, src.data_ptr(),
-                    (size_t)src.numel() * v.itemsize);
-    }
-
     void get_range(const std::string& name, int64_t start, int64_t count,
                    at::Tensor out) {
         HostVar& v = var(name);
-        TORCH_CHECK(!v.is_csr, "ddstore get: use get_csr for CSR variables");
-        TORCH_CHECK(out.is_contiguous() && out.device().is_cpu(),
-                    "ddstore get: output must be C-contiguous on CPU");
-        TORCH_CHECK(dds_itemsize(dds_type_of(out)) == v.itemsize,
-                    "ddstore get: itemsize mismatch");
-        TORCH_CHECK(out.numel() == count * v.row_elems, "ddstore get: shape mismatch");
+        check_range_out(v, out, count, true);
         check_peers(v);
-        int64_t ntotal = v.prefix[nparts_];
-        TORCH_CHECK(start >= 0 && start < ntotal, "Invalid start on target");
-        int target = owner_of_host(v.prefix, start);
-        TORCH_CHECK(start + count <= v.prefix[target + 1], "Invalid count on target");
-        const char* src = (const char*)v.peers[target] +
-                          (start - v.prefix[target]) * v.row_elems * v.itemsize;
-        size_t nb = (size_t)count * v.row_elems * v.itemsize;
+        const auto [src, nb] = owned_range(v, start, count);
         std::memcpy(out.data_ptr(), src, nb);
-        v.n_gather += 1;
-        v.rows_gathered += count;
-        v.bytes_gathered += nb;
+        v.count(count, (int64_t)nb);
     }
 
     void gather(const std::string& name, const at::Tensor& idx, at::Tensor out) {
@@ -1434,9 +1281,7 @@ public:
             }
         });
         copy_rows_fence();
-        v.n_gather += 1;
-        v.rows_gathered += nidx;
-        v.bytes_gathered += nidx * rb;
+        v.count(nidx, nidx * rb);
     }
 
     void gather_csr(const std::string& name, const at::Tensor& idx,
@@ -1491,9 +1336,7 @@ public:
         });
         v.oob_skipped += oob.load();
         v.cap_skipped += capskip.load();
-        v.n_gather += 1;
-        v.rows_gathered += idx.numel();
-        v.bytes_gathered += elems.load() * eb;  // true gathered bytes
+        v.count(idx.numel(), elems.load() * eb);  // true gathered bytes
     }
 
     void scatter_local(const std::string& name, const at::Tensor& local_idx,
@@ -1520,8 +1363,8 @@ public:
 
     at::Tensor local_shard(const std::string& name) {
         HostVar& v = var(name);
-        int64_t n = v.is_csr ? v.nelems_local : v.nrows_local;
-        return at::from_blob(v.base, {n, v.row_elems}, at::TensorOptions().dtype(v.st));
+        return at::from_blob(v.base, {v.local_count(), v.row_elems},
+                             at::TensorOptions().dtype(v.st));
     }
 
     void epoch_begin() { fsm_.begin(); }
@@ -1532,17 +1375,8 @@ public:
     bool epoch_active() const { return fsm_.fence_active; }
 
     void check_strict() {
-        for (auto& kv : vars_) {
-            HostVar& v = kv.second;
-            TORCH_CHECK(v.oob_skipped == 0, "ddstore strict: variable '",
-                        kv.first, "': ", v.oob_skipped,
-                        " out-of-range sample indices were skipped "
-                        "(DDSTORE_STRICT=1)");
-            TORCH_CHECK(v.cap_skipped == 0, "ddstore strict: variable '",
-                        kv.first, "': ", v.cap_skipped,
-                        " CSR samples skipped: output capacity buffer too "
-                        "small (DDSTORE_STRICT=1)");
-        }
+        for (auto& kv : vars_)
+            strict_check(kv.first, kv.second.oob_skipped, kv.second.cap_skipped);
     }
 
     void reset_counters(const std::string& name) {
@@ -1553,19 +1387,7 @@ public:
 
     py::dict query(const std::string& name) {
         HostVar& v = var(name);
-        py::dict d;
-        d["nrows_local"] = v.nrows_local;
-        d["nrows_total"] = v.prefix[nparts_];
-        d["disp"] = v.row_elems;
-        d["itemsize"] = v.itemsize;
-        d["is_csr"] = v.is_csr;
-        d["prefix"] = v.prefix;
-        if (v.is_csr) {
-            d["nelems_local"] = v.nelems_local;
-            d["elem_prefix"] = v.elem_prefix;
-        }
-        d["n_gather"] = v.n_gather;
-        d["rows_gathered"] = v.rows_gathered;
+        py::dict d = query_layout(v);
         d["bytes_gathered"] = v.bytes_gathered;
         d["oob_skipped"] = v.oob_skipped;
         d["cap_skipped"] = v.cap_skipped;
@@ -1631,7 +1453,34 @@ private:
         if (v.base && v.base != MAP_FAILED) munmap(v.base, v.base_bytes);
         if (v.creator) shm_unlink(v.shm_name.c_str());
         v.base = nullptr;
-        v.active = false;
+    }
+
+    // The one registration body (arguments as describe_var): create the shm
+    // segment and fill it from `src` or with zeros.
+    std::string register_var(const std::string& name, const char* op,
+                             const at::Tensor* src, at::ScalarType st, int64_t row_elems,
+                             int64_t n_local, const std::vector<int64_t>& counts,
+                             const CsrShape* csr) {
+        check_new(name);
+        HostVar v;
+        describe_var(v, op, src, st, row_elems, n_local, counts, csr, true);
+        if (csr) v.goff = csr->goff;
+        create_shm(v, name, v.shard_bytes());
+        if (src)
+            std::memcpy(v.base, src->data_ptr(), (size_t)src->numel() * v.itemsize);
+        else
+            std::memset(v.base, 0, v.base_bytes);
+        try_collapse_hugepages(v.base, v.base_bytes);
+        std::string n = v.shm_name;
+        vars_[name] = std::move(v);
+        return n;
+    }
+
+    // body of update and update_elems
+    void fill(const std::string& name, const at::Tensor& src, int64_t offset, bool elems) {
+        HostVar& v = var(name);
+        const int64_t at = check_update(v, elems, src, offset, true);
+        std::memcpy((char*)v.base + at, src.data_ptr(), (size_t)src.numel() * v.itemsize);
     }
 
     std::string session_;

@@ -55,78 +55,90 @@ struct GatherDirK {
     const void* base[DDS_DIR_KPARTS];
 };
 
-// Gather `nidx` fixed-stride rows (row = `row_elems` elements of dtype
-// `in_t`) addressed by global row ids `d_idx` from the sharded store
-// described by (`d_peer_base`, `d_prefix`, `nparts`), packing them
-// contiguously into `d_out` with dtype `out_t`.
-//   d_peer_base : device array[nparts]   -- shard base pointers (self + IPC peers)
-//   d_prefix    : device array[nparts+1] -- global row prefix sums, prefix[0]=0
-//   h_peer_base : HOST copy of d_peer_base (array[nparts])
-//   h_prefix    : HOST copy of d_prefix (array[nparts+1])
+// Element size in bytes of a DDSType tag.
+inline int64_t dds_itemsize(int t) {
+    switch (t) {
+        case DDS_U8: case DDS_F8E4M3: case DDS_F8E5M2: return 1;
+        case DDS_F16: case DDS_BF16: return 2;
+        case DDS_I32: case DDS_F32: return 4;
+        default: return 8;
+    }
+}
+
+// Owner directory of a fixed-stride variable, in both copies:
+//   d_base   : device array[nparts]   -- shard base pointers (self + IPC peers)
+//   d_prefix : device array[nparts+1] -- global row prefix sums, prefix[0]=0
+//   h_base   : HOST copy of d_base (array[nparts])
+//   h_prefix : HOST copy of d_prefix (array[nparts+1])
 // The host copies feed the kernel-argument directory of the tiled kernel
 // (nparts <= DDS_DIR_KPARTS); the device copies serve the LDS-staged
 // variant and the scalar fallbacks. Both must describe the same shards.
+struct RowDir {
+    const void* const* d_base;
+    const int64_t* d_prefix;
+    const void* const* h_base;
+    const int64_t* h_prefix;
+    int nparts;
+};
+
+// Owner directory of a CSR variable (device memory throughout): sample `g`
+// owns elements [d_goff[g], d_goff[g+1]) of the global element space.
+//   d_base          : array[nparts]   -- shard base pointers
+//   d_sample_prefix : array[nparts+1] -- per-rank sample-count prefix sums
+//   d_elem_prefix   : array[nparts+1] -- per-rank element-count prefix sums
+//   d_goff          : array[nsamples_total+1] -- replicated element offsets
+struct CsrDir {
+    const void* const* d_base;
+    const int64_t* d_sample_prefix;
+    const int64_t* d_elem_prefix;
+    int nparts;
+    const int64_t* d_goff;
+    int64_t nsamples_total;
+};
+
+// What a fetch does to each element on the way. !on: byte move if the
+// dtypes agree, else a numeric cast. on: out = cast(in) * scale + shift (f32
+// math; float output dtypes only) -- data-loader normalization folded into
+// the fetch. With d_scale != nullptr the pair is per column instead:
+// out[r][c] = cast(in[r][c]) * d_scale[c] + d_shift[c], same rounding
+// contract; d_scale and d_shift are device arrays of row_elems floats each,
+// 16-B aligned, on the store device, and `scale` / `shift` are unused.
+struct Affine {
+    bool on = false;
+    float scale = 1.0f, shift = 0.0f;
+    const float* d_scale = nullptr;
+    const float* d_shift = nullptr;
+};
+
+// Gather `nidx` fixed-stride rows (row = `row_elems` elements of dtype
+// `in_t`) addressed by global row ids `d_idx` from the sharded store
+// described by `dir`, packing them contiguously into `d_out` with dtype
+// `out_t` through `xf`.
 // d_oob: device counter incremented once per out-of-range index (the row is
 // skipped instead of read out of bounds; checked lazily via query()).
-void gather_rows(hipStream_t stream,
-                 const void* const* d_peer_base,
-                 const int64_t* d_prefix,
-                 const void* const* h_peer_base,
-                 const int64_t* h_prefix, int nparts,
+void gather_rows(hipStream_t stream, const RowDir& dir,
                  const int64_t* d_idx, int64_t nidx,
-                 int64_t row_elems, int in_t, int out_t,
+                 int64_t row_elems, int in_t, int out_t, const Affine& xf,
                  void* d_out, unsigned long long* d_oob);
 
-// Fused affine gather: out = cast(in) * scale + shift (f32 math; float
-// output dtypes only) -- data-loader normalization folded into the fetch.
-// Directory arguments as for gather_rows.
-void gather_rows_affine(hipStream_t stream,
-                        const void* const* d_peer_base,
-                        const int64_t* d_prefix,
-                        const void* const* h_peer_base,
-                        const int64_t* h_prefix, int nparts,
-                        const int64_t* d_idx, int64_t nidx,
-                        int64_t row_elems, int in_t, int out_t,
-                        float scale, float shift,
-                        void* d_out, unsigned long long* d_oob);
-
-// Per-column form of gather_rows_affine: out[r][c] = cast(in[r][c]) *
-// d_scale[c] + d_shift[c], same rounding contract. d_scale and d_shift are
-// device arrays of row_elems floats each, 16-B aligned, on the store device.
-void gather_rows_affine_cols(hipStream_t stream,
-                             const void* const* d_peer_base,
-                             const int64_t* d_prefix,
-                             const void* const* h_peer_base,
-                             const int64_t* h_prefix, int nparts,
-                             const int64_t* d_idx, int64_t nidx,
-                             int64_t row_elems, int in_t, int out_t,
-                             const float* d_scale, const float* d_shift,
-                             void* d_out, unsigned long long* d_oob);
-
-// CSR (variable-length record) gather: sample `g` owns elements
-// [d_goff[g], d_goff[g+1]) of the global element space; each element is
-// `elem_bytes` bytes (= disp * itemsize). Output element offsets per sample
-// are provided in d_out_off (exclusive scan, [nidx+1]). `cap_elems` is the
+// CSR (variable-length record) gather: each element is `elem_bytes` bytes
+// (= disp * itemsize). Output element offsets per sample are provided in
+// d_out_off (exclusive scan, [nidx+1]). `cap_elems` is the
 // output buffer's capacity in elements: a non-empty sample whose slice would
 // end past it is SKIPPED and counted in d_ctrs[DDS_CTR_CAP] (never written
 // OOB). An empty sample writes nothing and is never counted.
-//   d_sample_prefix : array[nparts+1] -- per-rank sample-count prefix sums
-//   d_elem_prefix   : array[nparts+1] -- per-rank element-count prefix sums
-void gather_csr(hipStream_t stream,
-                const void* const* d_peer_base,
-                const int64_t* d_sample_prefix,
-                const int64_t* d_elem_prefix, int nparts,
-                const int64_t* d_goff,
+void gather_csr(hipStream_t stream, const CsrDir& dir,
                 const int64_t* d_idx, int64_t nidx,
                 const int64_t* d_out_off,
                 int64_t elem_bytes, int64_t cap_elems,
                 void* d_out, unsigned long long* d_ctrs);
 
-// lens[i] = goff[idx[i]+1] - goff[idx[i]] (CSR gather plan helper). If
-// d_elems != nullptr the true total (sum of lens) is accumulated into it
-// (wave-reduced; used by gather_csr_fast for exact byte stats).
-void csr_lens(hipStream_t stream, const int64_t* d_goff, const int64_t* d_idx,
-              int64_t nidx, int64_t nsamples, int64_t* d_lens,
+// lens[i] = goff[idx[i]+1] - goff[idx[i]] (CSR gather plan helper; reads
+// dir.d_goff and dir.nsamples_total only). If d_elems != nullptr the true
+// total (sum of lens) is accumulated into it (wave-reduced; used by
+// gather_csr_fast for exact byte stats).
+void csr_lens(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+              int64_t nidx, int64_t* d_lens,
               unsigned long long* d_oob, unsigned long long* d_elems);
 
 // Balanced one-call CSR fetch: three tiny plan kernels (per-tile lens+scan,
@@ -147,10 +159,7 @@ void csr_lens(hipStream_t stream, const int64_t* d_goff, const int64_t* d_idx,
 // skipped samples), whatever the buffer held before.
 size_t csr_plan_scratch_bytes(int64_t nidx);
 int64_t csr_item_elems(int64_t elem_bytes);
-void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
-                         const int64_t* d_sample_prefix,
-                         const int64_t* d_elem_prefix, int nparts,
-                         const int64_t* d_goff, int64_t nsamples_total,
+void gather_csr_balanced(hipStream_t stream, const CsrDir& dir,
                          const int64_t* d_idx, int64_t nidx,
                          int64_t elem_bytes, int64_t cap_elems,
                          int64_t* d_out_off, void* d_out,
@@ -159,39 +168,22 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
 
 // Padded CSR gather, ONE launch: sample d_idx[s] is written to row s of a
 // dense (nidx, max_len, row_elems) output of dtype `out_t` -- its first
-// min(len, max_len) elements through the byte move / cast / affine
-// (affine: out = cast(in) * scale + shift, f32 math, f32/f16/bf16 outputs
-// only), the rest of the row filled with the pad. `pad_bits` holds the raw
-// bits of ONE output element in its low bytes; the kernel broadcasts them
-// and applies neither cast nor affine to them. d_lengths[s] receives the
-// true stored length (not clipped to max_len). An out-of-range index gives
-// an all-pad row, length 0, and one count in d_ctrs[DDS_CTR_OOB]. The true
-// gathered elements, sum(min(len, max_len)), accumulate into
-// d_ctrs[DDS_CTR_ELEMS]. Every output element is written exactly once; no
-// scratch, no host reads of device data. Directory arguments as gather_csr.
-void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
-                       const int64_t* d_sample_prefix,
-                       const int64_t* d_elem_prefix, int nparts,
-                       const int64_t* d_goff, int64_t nsamples_total,
+// min(len, max_len) elements through the byte move / cast / affine `xf`
+// (f32/f16/bf16 outputs only when xf.on; a column of the per-column form is
+// an element's flat position in [0, row_elems)), the rest of the row filled
+// with the pad. `pad_bits` holds the raw bits of ONE output element in its
+// low bytes; the kernel broadcasts them and applies neither cast nor affine
+// to them. d_lengths[s] receives the true stored length (not clipped to
+// max_len). An out-of-range index gives an all-pad row, length 0, and one
+// count in d_ctrs[DDS_CTR_OOB]. The true gathered elements, sum(min(len,
+// max_len)), accumulate into d_ctrs[DDS_CTR_ELEMS]. Every output element is
+// written exactly once; no scratch, no host reads of device data.
+void gather_csr_padded(hipStream_t stream, const CsrDir& dir,
                        const int64_t* d_idx, int64_t nidx,
                        int64_t row_elems, int64_t max_len, int in_t, int out_t,
-                       bool affine, float scale, float shift, uint64_t pad_bits,
+                       const Affine& xf, uint64_t pad_bits,
                        void* d_out, int64_t* d_lengths,
                        unsigned long long* d_ctrs);
-
-// Vector form of gather_csr_padded's affine: column c of every element (its
-// flat position in [0, row_elems)) is scaled by d_scale[c] and shifted by
-// d_shift[c]; arrays as for gather_rows_affine_cols. Everything else,
-// the untouched pad included, as gather_csr_padded with affine = true.
-void gather_csr_padded_cols(hipStream_t stream, const void* const* d_peer_base,
-                            const int64_t* d_sample_prefix,
-                            const int64_t* d_elem_prefix, int nparts,
-                            const int64_t* d_goff, int64_t nsamples_total,
-                            const int64_t* d_idx, int64_t nidx,
-                            int64_t row_elems, int64_t max_len, int in_t, int out_t,
-                            const float* d_scale, const float* d_shift,
-                            uint64_t pad_bits, void* d_out, int64_t* d_lengths,
-                            unsigned long long* d_ctrs);
 
 // Column statistics of one local shard, viewed as a row-major (rows,
 // row_elems) array of dtype `in_t` (for a CSR variable: its elements). Writes
@@ -216,7 +208,7 @@ void column_stats(hipStream_t stream, const void* d_base, int64_t rows,
 // k_csr_plan2 as they are, so bad indices count in d_ctrs[DDS_CTR_OOB] and the
 // requested total is ADDED to d_ctrs[DDS_CTR_ELEMS]: the gather that follows
 // takes back what it drops. d_scratch: csr_plan_scratch_bytes(nidx) bytes.
-void csr_offsets(hipStream_t stream, const int64_t* d_goff, int64_t nsamples_total,
+void csr_offsets(hipStream_t stream, const CsrDir& dir,
                  const int64_t* d_idx, int64_t nidx, int64_t* d_out_off,
                  void* d_scratch, unsigned long long* d_ctrs);
 
@@ -228,10 +220,8 @@ void csr_offsets(hipStream_t stream, const int64_t* d_goff, int64_t nsamples_tot
 // (coo) or at that row of an (ecap, 2) output. A graph with edges that are
 // not written counts once in d_ctrs[DDS_CTR_CAP] and its edges are subtracted
 // from d_ctrs[DDS_CTR_ELEMS]. Slots of no kept edge are left to graph_fill.
-void gather_csr_relabel(hipStream_t stream, const void* const* d_peer_base,
-                        const int64_t* d_sample_prefix,
-                        const int64_t* d_elem_prefix, int nparts,
-                        const int64_t* d_goff, const int64_t* d_idx, int64_t nidx,
+void gather_csr_relabel(hipStream_t stream, const CsrDir& dir,
+                        const int64_t* d_idx, int64_t nidx,
                         const int64_t* d_ptr, const int64_t* d_edge_ptr,
                         int64_t ncap, int64_t ecap, int in_t, int out_t, bool coo,
                         void* d_out, unsigned long long* d_ctrs);

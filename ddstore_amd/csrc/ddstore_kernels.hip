@@ -1567,24 +1567,6 @@ k_colstats_final(const T* __restrict__ base, int64_t R, int64_t D,
     }
 }
 
-inline int dds_itemsize(int t) {
-    switch (t) {
-        case DDS_U8: case DDS_F8E4M3: case DDS_F8E5M2: return 1;
-        case DDS_F16: case DDS_BF16: return 2;
-        case DDS_I32: case DDS_F32: return 4;
-        default: return 8;
-    }
-}
-
-// Both copies of one variable's directory (see ddstore_kernels.h).
-struct DirArgs {
-    const void* const* d_pb;
-    const int64_t* d_pf;
-    const void* const* h_pb;
-    const int64_t* h_pf;
-    int np;
-};
-
 // A/B knobs of the fixed-stride gather, read once (docs/API.md):
 //   DDSTORE_GATHER_KERNEL=legacy|tiled  force one kernel family (default:
 //                                       by row size, see kTiledMinCpr)
@@ -1659,7 +1641,7 @@ constexpr int64_t kTiledMinCpr = 8;
 // Launch the tiled core if the shape is eligible; false = caller falls back.
 // `re` = elements per row, counted in Tin/Tout elements.
 template <typename Tin, typename Tout, typename Xf>
-bool launch_tiled(hipStream_t stream, const DirArgs& d, const int64_t* idx,
+bool launch_tiled(hipStream_t stream, const RowDir& d, const int64_t* idx,
                   int64_t n, int64_t re, Xf xf, Tout* out,
                   unsigned long long* oob) {
     constexpr int VEC = 16 / sizeof(Tout);
@@ -1682,38 +1664,39 @@ bool launch_tiled(hipStream_t stream, const DirArgs& d, const int64_t* idx,
     int64_t grid = (ntiles + (kBlock / 64) - 1) / (kBlock / 64);
     if (grid > blocks_max) grid = blocks_max;
 
-    if (d.np <= DDS_DIR_KPARTS && !kn.dir_lds) {
+    if (d.nparts <= DDS_DIR_KPARTS && !kn.dir_lds) {
         GatherDirK dir;
-        const int64_t total = d.h_pf[d.np];
+        const int64_t total = d.h_prefix[d.nparts];
         for (int k = 0; k <= DDS_DIR_KPARTS; ++k)
-            dir.prefix[k] = k < d.np ? d.h_pf[k] : total;
+            dir.prefix[k] = k < d.nparts ? d.h_prefix[k] : total;
         for (int k = 0; k < DDS_DIR_KPARTS; ++k)
-            dir.base[k] = k < d.np ? d.h_pb[k] : nullptr;
+            dir.base[k] = k < d.nparts ? d.h_base[k] : nullptr;
         hipLaunchKernelGGL((k_gather_tiled<Tin, Tout, Xf, false>), dim3((unsigned)grid),
-                           dim3(kBlock), 0, stream, dir, d.d_pb, d.d_pf, d.np, idx, n,
-                           ntiles, (uint32_t)cpr, (uint32_t)tr, xf, out, oob);
+                           dim3(kBlock), 0, stream, dir, d.d_base, d.d_prefix, d.nparts,
+                           idx, n, ntiles, (uint32_t)cpr, (uint32_t)tr, xf, out, oob);
     } else {
         GatherDirK dir = {};
         hipLaunchKernelGGL((k_gather_tiled<Tin, Tout, Xf, true>), dim3((unsigned)grid),
-                           dim3(kBlock), 0, stream, dir, d.d_pb, d.d_pf, d.np, idx, n,
-                           ntiles, (uint32_t)cpr, (uint32_t)tr, xf, out, oob);
+                           dim3(kBlock), 0, stream, dir, d.d_base, d.d_prefix, d.nparts,
+                           idx, n, ntiles, (uint32_t)cpr, (uint32_t)tr, xf, out, oob);
     }
     return true;
 }
 
 template <typename Tin, typename Tout, int VEC, typename Xf>
-void launch_oneshot(hipStream_t stream, const DirArgs& d, const int64_t* idx,
+void launch_oneshot(hipStream_t stream, const RowDir& d, const int64_t* idx,
                     int64_t n, int64_t re, Xf xf, Tout* out,
                     unsigned long long* oob) {
     const int grid = n_blocks(n * (re / VEC));
     hipLaunchKernelGGL((k_gather_oneshot<Tin, Tout, VEC, Xf>), dim3(grid), dim3(kBlock),
-                       0, stream, d.d_pb, d.d_pf, d.np, idx, n, re, xf, out, oob);
+                       0, stream, d.d_base, d.d_prefix, d.nparts, idx, n, re, xf, out,
+                       oob);
 }
 
 // Cast and affine gathers: tiled if eligible, else the one-shot kernel with
 // 16-B stores if the row and the output pointer allow, else element-wise.
 template <typename Tin, typename Tout, typename Xf>
-void launch_gather(hipStream_t stream, const DirArgs& d, const int64_t* idx,
+void launch_gather(hipStream_t stream, const RowDir& d, const int64_t* idx,
                    int64_t n, int64_t re, Xf xf, Tout* out,
                    unsigned long long* oob) {
     constexpr int VEC = 16 / sizeof(Tout);
@@ -1761,71 +1744,17 @@ void dispatch_group(int group, F&& f) {
 
 } // namespace
 
-void gather_rows_affine(hipStream_t stream,
-                        const void* const* d_peer_base,
-                        const int64_t* d_prefix,
-                        const void* const* h_peer_base,
-                        const int64_t* h_prefix, int nparts,
-                        const int64_t* d_idx, int64_t nidx,
-                        int64_t row_elems, int in_t, int out_t,
-                        float scale, float shift,
-                        void* d_out, unsigned long long* d_oob) {
-    if (nidx == 0 || row_elems == 0) return;
-    const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
-    dispatch_dtype(in_t, [&](auto ti) {
-        dispatch_dtype(out_t, [&](auto to) {
-            using Tin = typename decltype(ti)::type;
-            using Tout = typename decltype(to)::type;
-            // float outputs only
-            if constexpr (std::is_same_v<Tout, float> || std::is_same_v<Tout, __half> ||
-                          std::is_same_v<Tout, __hip_bfloat16>)
-                launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems,
-                                         XfAffine{scale, shift}, (Tout*)d_out, d_oob);
-        });
-    });
-}
-
-void gather_rows_affine_cols(hipStream_t stream,
-                             const void* const* d_peer_base,
-                             const int64_t* d_prefix,
-                             const void* const* h_peer_base,
-                             const int64_t* h_prefix, int nparts,
-                             const int64_t* d_idx, int64_t nidx,
-                             int64_t row_elems, int in_t, int out_t,
-                             const float* d_scale, const float* d_shift,
-                             void* d_out, unsigned long long* d_oob) {
-    if (nidx == 0 || row_elems == 0) return;
-    const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
-    dispatch_dtype(in_t, [&](auto ti) {
-        dispatch_dtype(out_t, [&](auto to) {
-            using Tin = typename decltype(ti)::type;
-            using Tout = typename decltype(to)::type;
-            // float outputs only
-            if constexpr (std::is_same_v<Tout, float> || std::is_same_v<Tout, __half> ||
-                          std::is_same_v<Tout, __hip_bfloat16>)
-                launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems,
-                                         XfAffineCol{d_scale, d_shift}, (Tout*)d_out,
-                                         d_oob);
-        });
-    });
-}
-
-void gather_rows(hipStream_t stream,
-                 const void* const* d_peer_base,
-                 const int64_t* d_prefix,
-                 const void* const* h_peer_base,
-                 const int64_t* h_prefix, int nparts,
+void gather_rows(hipStream_t stream, const RowDir& dir,
                  const int64_t* d_idx, int64_t nidx,
-                 int64_t row_elems, int in_t, int out_t,
+                 int64_t row_elems, int in_t, int out_t, const Affine& xf,
                  void* d_out, unsigned long long* d_oob) {
     if (nidx == 0 || row_elems == 0) return;
-    const DirArgs dir{d_peer_base, d_prefix, h_peer_base, h_prefix, nparts};
     const int64_t row_bytes = row_elems * dds_itemsize(in_t);
     // the uint4/VecT paths require a 16/32-B-aligned output pointer; an
     // offset view (e.g. buf[1:]) falls through to the cast/scalar kernels,
     // whose own vector path re-checks alignment
     const uintptr_t out_align = (uintptr_t)d_out;
-    if (in_t == out_t && row_bytes % 16 == 0 && out_align % 16 == 0) {
+    if (!xf.on && in_t == out_t && row_bytes % 16 == 0 && out_align % 16 == 0) {
         // NB: a thread-per-row variant (one idx load, all chunks in flight
         // per thread) was measured SLOWER on MI355X for <=64 B rows (7.5 vs
         // 6.1 us at B=131072): fewer, fatter threads lose more to the
@@ -1858,26 +1787,35 @@ void gather_rows(hipStream_t stream,
         dispatch_dtype(out_t, [&](auto to) {
             using Tin = typename decltype(ti)::type;
             using Tout = typename decltype(to)::type;
-            launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems, XfCast{},
-                                     (Tout*)d_out, d_oob);
+            auto launch = [&](auto x) {
+                launch_gather<Tin, Tout>(stream, dir, d_idx, nidx, row_elems, x,
+                                         (Tout*)d_out, d_oob);
+            };
+            if (!xf.on) {
+                launch(XfCast{});
+            } else if constexpr (std::is_same_v<Tout, float> ||
+                                 std::is_same_v<Tout, __half> ||
+                                 std::is_same_v<Tout, __hip_bfloat16>) {
+                // float outputs only
+                if (xf.d_scale)
+                    launch(XfAffineCol{xf.d_scale, xf.d_shift});
+                else
+                    launch(XfAffine{xf.scale, xf.shift});
+            }
         });
     });
 }
 
-void csr_lens(hipStream_t stream, const int64_t* d_goff, const int64_t* d_idx,
-              int64_t nidx, int64_t nsamples, int64_t* d_lens,
+void csr_lens(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+              int64_t nidx, int64_t* d_lens,
               unsigned long long* d_oob, unsigned long long* d_elems) {
     if (nidx == 0) return;
     hipLaunchKernelGGL(k_csr_lens, dim3(n_blocks(nidx)), dim3(kBlock), 0, stream,
-                       d_goff, d_idx, nidx, nsamples, d_lens, d_oob, d_elems);
+                       dir.d_goff, d_idx, nidx, dir.nsamples_total, d_lens, d_oob,
+                       d_elems);
 }
 
-
-void gather_csr(hipStream_t stream,
-                const void* const* d_peer_base,
-                const int64_t* d_sample_prefix,
-                const int64_t* d_elem_prefix, int nparts,
-                const int64_t* d_goff,
+void gather_csr(hipStream_t stream, const CsrDir& dir,
                 const int64_t* d_idx, int64_t nidx,
                 const int64_t* d_out_off,
                 int64_t elem_bytes, int64_t cap_elems,
@@ -1904,10 +1842,10 @@ void gather_csr(hipStream_t stream,
         using U = typename decltype(unit)::type;
         dispatch_group<8, 16, 32, 64, 256>(group, [&](auto G) {
             hipLaunchKernelGGL((k_gather_csr_wave<U, G()>), dim3(grid), dim3(kBlock), 0,
-                               stream, d_peer_base, d_sample_prefix, d_elem_prefix,
-                               nparts, d_goff, d_idx, nidx, d_out_off,
-                               elem_bytes / (int64_t)sizeof(U), cap_elems, (U*)d_out,
-                               d_ctrs);
+                               stream, dir.d_base, dir.d_sample_prefix,
+                               dir.d_elem_prefix, dir.nparts, dir.d_goff, d_idx, nidx,
+                               d_out_off, elem_bytes / (int64_t)sizeof(U), cap_elems,
+                               (U*)d_out, d_ctrs);
         });
     };
     if (elem_bytes % 16 == 0 && oa % 16 == 0) {
@@ -1921,24 +1859,16 @@ void gather_csr(hipStream_t stream,
     }
 }
 
-// Both forms of the padded gather: `affine` false = byte move or cast, true =
-// the scalar pair, or the per-column vectors if d_scale is not null.
-static void csr_padded_impl(hipStream_t stream, const void* const* d_peer_base,
-                            const int64_t* d_sample_prefix,
-                            const int64_t* d_elem_prefix, int nparts,
-                            const int64_t* d_goff, int64_t nsamples_total,
-                            const int64_t* d_idx, int64_t nidx,
-                            int64_t row_elems, int64_t max_len, int in_t, int out_t,
-                            bool affine, float scale, float shift,
-                            const float* d_scale, const float* d_shift,
-                            uint64_t pad_bits, void* d_out, int64_t* d_lengths,
-                            unsigned long long* d_ctrs) {
+void gather_csr_padded(hipStream_t stream, const CsrDir& dir,
+                       const int64_t* d_idx, int64_t nidx,
+                       int64_t row_elems, int64_t max_len, int in_t, int out_t,
+                       const Affine& xf, uint64_t pad_bits,
+                       void* d_out, int64_t* d_lengths,
+                       unsigned long long* d_ctrs) {
     if (nidx == 0) return;
     if (row_elems == 0 || max_len == 0) {
         // no payload to move: lengths and the bad-index count only
-        hipLaunchKernelGGL(k_csr_lens, dim3(n_blocks(nidx)), dim3(kBlock), 0, stream,
-                           d_goff, d_idx, nidx, nsamples_total, d_lengths,
-                           d_ctrs + DDS_CTR_OOB, (unsigned long long*)nullptr);
+        csr_lens(stream, dir, d_idx, nidx, d_lengths, d_ctrs + DDS_CTR_OOB, nullptr);
         return;
     }
     // the pad's raw bits, replicated over one 16-B output chunk
@@ -1949,7 +1879,7 @@ static void csr_padded_impl(hipStream_t stream, const void* const* d_peer_base,
     __builtin_memcpy(&pad16, pb, 16);
     const uintptr_t oa = (uintptr_t)d_out;
     // `disp` counts Tin/Tout units per element
-    auto launch = [&](auto ti, auto to, auto vec, auto xf, int64_t disp, bool aligned) {
+    auto launch = [&](auto ti, auto to, auto vec, auto x, int64_t disp, bool aligned) {
         using Tin = typename decltype(ti)::type;
         using Tout = typename decltype(to)::type;
         constexpr int VEC = decltype(vec)::value;
@@ -1960,14 +1890,15 @@ static void csr_padded_impl(hipStream_t stream, const void* const* d_peer_base,
         if (cpr > 64 && nidx < 4096) lg = 8;
         const int64_t gpb = kBlock >> lg;
         const int64_t b = (nidx + gpb - 1) / gpb;
-        hipLaunchKernelGGL((k_gather_csr_padded<Tin, Tout, VEC, decltype(xf)>),
+        hipLaunchKernelGGL((k_gather_csr_padded<Tin, Tout, VEC, decltype(x)>),
                            dim3((unsigned)(b < kMaxBlocks ? b : kMaxBlocks)),
-                           dim3(kBlock), 0, stream, d_peer_base, d_sample_prefix,
-                           d_elem_prefix, nparts, d_goff, d_idx, nidx, disp, max_len,
-                           lg, aligned, xf, pad16, (Tout*)d_out, d_lengths, d_ctrs);
+                           dim3(kBlock), 0, stream, dir.d_base, dir.d_sample_prefix,
+                           dir.d_elem_prefix, dir.nparts, dir.d_goff, d_idx, nidx, disp,
+                           max_len, lg, aligned, x, pad16, (Tout*)d_out, d_lengths,
+                           d_ctrs);
     };
     const int64_t elem_bytes = row_elems * dds_itemsize(in_t);
-    if (!affine && in_t == out_t && elem_bytes % 16 == 0 && oa % 16 == 0) {
+    if (!xf.on && in_t == out_t && elem_bytes % 16 == 0 && oa % 16 == 0) {
         // byte move: one uint4 is the unit, so VEC = 1
         launch(TypeTag<uint4>{}, TypeTag<uint4>{}, std::integral_constant<int, 1>{},
                XfIdentity{}, elem_bytes / 16, true);
@@ -1975,59 +1906,31 @@ static void csr_padded_impl(hipStream_t stream, const void* const* d_peer_base,
     }
     // 16-B stores if the output pointer and the row allow (vector loads if
     // the element width allows as well), else element-wise
-    auto launch_xf = [&](auto ti, auto to, auto xf) {
+    auto launch_xf = [&](auto ti, auto to, auto x) {
         using Tout = typename decltype(to)::type;
         constexpr int VEC = 16 / sizeof(Tout);
         if (oa % 16 == 0 && (max_len * row_elems) % VEC == 0)
-            launch(ti, to, std::integral_constant<int, VEC>{}, xf, row_elems,
+            launch(ti, to, std::integral_constant<int, VEC>{}, x, row_elems,
                    row_elems % VEC == 0);
         else
-            launch(ti, to, std::integral_constant<int, 1>{}, xf, row_elems, true);
+            launch(ti, to, std::integral_constant<int, 1>{}, x, row_elems, true);
     };
     dispatch_dtype(in_t, [&](auto ti) {
         dispatch_dtype(out_t, [&](auto to) {
             using Tout = typename decltype(to)::type;
-            if (!affine) {
+            if (!xf.on) {
                 launch_xf(ti, to, XfCast{});
             } else if constexpr (std::is_same_v<Tout, float> ||
                                  std::is_same_v<Tout, __half> ||
                                  std::is_same_v<Tout, __hip_bfloat16>) {
                 // float outputs only
-                if (d_scale)
-                    launch_xf(ti, to, XfAffineCol{d_scale, d_shift});
+                if (xf.d_scale)
+                    launch_xf(ti, to, XfAffineCol{xf.d_scale, xf.d_shift});
                 else
-                    launch_xf(ti, to, XfAffine{scale, shift});
+                    launch_xf(ti, to, XfAffine{xf.scale, xf.shift});
             }
         });
     });
-}
-
-void gather_csr_padded(hipStream_t stream, const void* const* d_peer_base,
-                       const int64_t* d_sample_prefix,
-                       const int64_t* d_elem_prefix, int nparts,
-                       const int64_t* d_goff, int64_t nsamples_total,
-                       const int64_t* d_idx, int64_t nidx,
-                       int64_t row_elems, int64_t max_len, int in_t, int out_t,
-                       bool affine, float scale, float shift, uint64_t pad_bits,
-                       void* d_out, int64_t* d_lengths,
-                       unsigned long long* d_ctrs) {
-    csr_padded_impl(stream, d_peer_base, d_sample_prefix, d_elem_prefix, nparts, d_goff,
-                    nsamples_total, d_idx, nidx, row_elems, max_len, in_t, out_t, affine,
-                    scale, shift, nullptr, nullptr, pad_bits, d_out, d_lengths, d_ctrs);
-}
-
-void gather_csr_padded_cols(hipStream_t stream, const void* const* d_peer_base,
-                            const int64_t* d_sample_prefix,
-                            const int64_t* d_elem_prefix, int nparts,
-                            const int64_t* d_goff, int64_t nsamples_total,
-                            const int64_t* d_idx, int64_t nidx,
-                            int64_t row_elems, int64_t max_len, int in_t, int out_t,
-                            const float* d_scale, const float* d_shift,
-                            uint64_t pad_bits, void* d_out, int64_t* d_lengths,
-                            unsigned long long* d_ctrs) {
-    csr_padded_impl(stream, d_peer_base, d_sample_prefix, d_elem_prefix, nparts, d_goff,
-                    nsamples_total, d_idx, nidx, row_elems, max_len, in_t, out_t, true,
-                    0.0f, 0.0f, d_scale, d_shift, pad_bits, d_out, d_lengths, d_ctrs);
 }
 
 // ---- column statistics (kernels: k_colstats_partial / k_colstats_final) ----
@@ -2099,10 +2002,7 @@ int64_t csr_item_elems(int64_t elem_bytes) {
     return ie > 0 ? ie : 1;
 }
 
-void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
-                         const int64_t* d_sample_prefix,
-                         const int64_t* d_elem_prefix, int nparts,
-                         const int64_t* d_goff, int64_t nsamples_total,
+void gather_csr_balanced(hipStream_t stream, const CsrDir& dir,
                          const int64_t* d_idx, int64_t nidx,
                          int64_t elem_bytes, int64_t cap_elems,
                          int64_t* d_out_off, void* d_out,
@@ -2119,14 +2019,14 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
     const bool dw = elem_bytes % 4 == 0 && oa % 4 == 0;
     const int64_t upe = dw ? elem_bytes / 4 : elem_bytes;  // units per elem
     const int g1 = (int)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-    hipLaunchKernelGGL(k_csr_plan1, dim3(g1), dim3(kBlock), 0, stream, d_goff,
-                       nsamples_total, d_idx, nidx, item_elems, lens_tmp,
+    hipLaunchKernelGGL(k_csr_plan1, dim3(g1), dim3(kBlock), 0, stream, dir.d_goff,
+                       dir.nsamples_total, d_idx, nidx, item_elems, lens_tmp,
                        e0_tmp, aggs, d_ctrs);
     hipLaunchKernelGGL(k_csr_plan2, dim3(1), dim3(kBlock), 0, stream, aggs,
                        ntiles, meta, d_ctrs);
     hipLaunchKernelGGL(k_csr_plan3, dim3(g1), dim3(kBlock), 0, stream,
-                       lens_tmp, e0_tmp, nidx, d_sample_prefix, d_elem_prefix,
-                       nparts, d_idx, item_elems, upe, cap_elems, aggs,
+                       lens_tmp, e0_tmp, nidx, dir.d_sample_prefix, dir.d_elem_prefix,
+                       dir.nparts, d_idx, item_elems, upe, cap_elems, aggs,
                        d_out_off, d_desc, desc_cap, d_ctrs);
     static const int item_group = [] {
         const char* e = getenv("DDSTORE_CSR_ITEM_GROUP");
@@ -2139,7 +2039,7 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
     auto launch = [&](auto unit, auto G) {
         using U = typename decltype(unit)::type;
         hipLaunchKernelGGL((k_gather_csr_items<U, G()>), dim3(g2), dim3(kBlock), 0,
-                           stream, d_peer_base, nparts, d_desc, meta, desc_cap,
+                           stream, dir.d_base, dir.nparts, d_desc, meta, desc_cap,
                            (U*)d_out);
     };
     if (dw) {
@@ -2151,7 +2051,7 @@ void gather_csr_balanced(hipStream_t stream, const void* const* d_peer_base,
     }
 }
 
-void csr_offsets(hipStream_t stream, const int64_t* d_goff, int64_t nsamples_total,
+void csr_offsets(hipStream_t stream, const CsrDir& dir,
                  const int64_t* d_idx, int64_t nidx, int64_t* d_out_off,
                  void* d_scratch, unsigned long long* d_ctrs) {
     if (nidx == 0) return;
@@ -2162,8 +2062,8 @@ void csr_offsets(hipStream_t stream, const int64_t* d_goff, int64_t nsamples_tot
     int64_t* meta = e0_tmp + nidx;
     const int g1 = (int)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
     // no work items here: one element per item keeps plan1's item count finite
-    hipLaunchKernelGGL(k_csr_plan1, dim3(g1), dim3(kBlock), 0, stream, d_goff,
-                       nsamples_total, d_idx, nidx, (int64_t)1, lens_tmp, e0_tmp,
+    hipLaunchKernelGGL(k_csr_plan1, dim3(g1), dim3(kBlock), 0, stream, dir.d_goff,
+                       dir.nsamples_total, d_idx, nidx, (int64_t)1, lens_tmp, e0_tmp,
                        aggs, d_ctrs);
     hipLaunchKernelGGL(k_csr_plan2, dim3(1), dim3(kBlock), 0, stream, aggs,
                        ntiles, meta, d_ctrs);
@@ -2171,10 +2071,8 @@ void csr_offsets(hipStream_t stream, const int64_t* d_goff, int64_t nsamples_tot
                        nidx, aggs, d_out_off);
 }
 
-void gather_csr_relabel(hipStream_t stream, const void* const* d_peer_base,
-                        const int64_t* d_sample_prefix,
-                        const int64_t* d_elem_prefix, int nparts,
-                        const int64_t* d_goff, const int64_t* d_idx, int64_t nidx,
+void gather_csr_relabel(hipStream_t stream, const CsrDir& dir,
+                        const int64_t* d_idx, int64_t nidx,
                         const int64_t* d_ptr, const int64_t* d_edge_ptr,
                         int64_t ncap, int64_t ecap, int in_t, int out_t, bool coo,
                         void* d_out, unsigned long long* d_ctrs) {
@@ -2186,9 +2084,10 @@ void gather_csr_relabel(hipStream_t stream, const void* const* d_peer_base,
         using Tin = typename decltype(ti)::type;
         using Tout = typename decltype(to)::type;
         hipLaunchKernelGGL((k_gather_csr_relabel<Tin, Tout, G, decltype(c)::value>),
-                           dim3(grid), dim3(kBlock), 0, stream, d_peer_base,
-                           d_sample_prefix, d_elem_prefix, nparts, d_goff, d_idx,
-                           nidx, d_ptr, d_edge_ptr, ncap, ecap, (Tout*)d_out, d_ctrs);
+                           dim3(grid), dim3(kBlock), 0, stream, dir.d_base,
+                           dir.d_sample_prefix, dir.d_elem_prefix, dir.nparts,
+                           dir.d_goff, d_idx, nidx, d_ptr, d_edge_ptr, ncap, ecap,
+                           (Tout*)d_out, d_ctrs);
     };
     auto launch_coo = [&](auto ti, auto to) {
         if (coo) launch(ti, to, std::true_type{});
