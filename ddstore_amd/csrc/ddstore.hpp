@@ -304,6 +304,11 @@ struct VarMeta {
     void* base = nullptr;
     size_t base_bytes = 0;
     std::vector<void*> peers;
+    // MX block-scaled storage (DeviceStore::init_mx): the element kind
+    // (DDSMxElem, -1 = not MX) and the logical row width. The variable itself
+    // is DDS_U8 with row_elems = mx_row_bytes(mx_disp, mx_elem).
+    int mx_elem = -1;
+    int64_t mx_disp = 0;
     // stats
     int64_t n_gather = 0, rows_gathered = 0, bytes_gathered = 0;
 
@@ -493,6 +498,41 @@ public:
         const CsrShape csr{nelems, nelems_all, goff_cpu};
         register_var(name, "init_csr", nullptr, st, row_elems, nsamples, nsamples_all,
                      &csr);
+    }
+
+    // MX variable (ddstore_kernels.h, "MX storage"): a zeroed u8 variable of
+    // packed rows plus the record that makes the gathers dequantize. Filled
+    // with update_mx.
+    void init_mx(const std::string& name, int64_t nrows, int64_t disp, int elem,
+                 std::vector<int64_t> nrows_all) {
+        TORCH_CHECK(elem >= DDS_MX_E4M3 && elem <= DDS_MX_E2M1,
+                    "ddstore init_mx: unknown element kind");
+        TORCH_CHECK(disp >= 1 && disp < (int64_t(1) << 30), "ddstore init_mx: bad disp");
+        register_var(name, "init_mx", nullptr, at::kByte, mx_row_bytes(disp, elem), nrows,
+                     nrows_all, nullptr);
+        DeviceVar& v = vars_[name];
+        v.mx_elem = elem;
+        v.mx_disp = disp;
+    }
+
+    // Quantize `src` (f32/f16/bf16, (n, disp), on the store device) into the
+    // packed rows [offset, offset + n) of the local shard. Local, like update.
+    void update_mx(const std::string& name, const at::Tensor& src, int64_t offset) {
+        RoctxRange rr_("ddstore::update_mx");
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.mx_elem >= 0, "ddstore update_mx: not an MX variable");
+        TORCH_CHECK(src.is_contiguous() && src.device().is_cuda() &&
+                        src.device().index() == device_,
+                    "ddstore update_mx: array must be C-contiguous on the store device");
+        const int in_t = dds_type_of(src);
+        TORCH_CHECK(float_out(in_t), "ddstore update_mx: array must be f32/f16/bf16");
+        const int64_t n = src.numel() / v.mx_disp;
+        TORCH_CHECK(src.numel() == n * v.mx_disp, "ddstore update_mx: shape mismatch");
+        TORCH_CHECK(offset >= 0 && offset + n <= v.nrows_local,
+                    "ddstore update_mx: out of range");
+        ddstore::quantize_rows_mx(stream(), src.data_ptr(), in_t, n, v.mx_disp, v.mx_elem,
+                                  (char*)v.base + offset * v.row_elems);
+        HIP_CHECK(hipStreamSynchronize(stream()));  // src may go once this returns
     }
 
     // purely local fills (reference ddstore.hpp:181-195), see check_update
@@ -1039,6 +1079,12 @@ private:
         const int64_t nidx = idx.numel();
         check_out(out, "ddstore gather: output must be a contiguous tensor on the store "
                        "device");
+        // an MX variable dequantizes; asked for uint8 it moves its packed
+        // rows like any u8 variable (what the reshuffle exchanges)
+        if (v.mx_elem >= 0 && !(out.scalar_type() == at::kByte && !xf.on)) {
+            gather_mx(v, idx, out, xf, scale, shift);
+            return;
+        }
         TORCH_CHECK(out.numel() == nidx * v.row_elems, "ddstore gather: shape mismatch");
         // byte move only for the SAME dds type (bool aliases u8); any other
         // dtype pair converts numerically -- a same-size pair like f16->bf16
@@ -1054,6 +1100,24 @@ private:
         ddstore::gather_rows(stream(), row_dir(v), idx.data_ptr<int64_t>(), nidx,
                              v.row_elems, v.dds_t, out_t, xf, out.data_ptr(), v.d_oob);
         v.count(nidx, nidx * v.row_elems * v.itemsize);
+    }
+
+    // gather_fixed for an MX variable: logical width, float outputs only,
+    // packed bytes counted.
+    void gather_mx(DeviceVar& v, const at::Tensor& idx, at::Tensor& out, Affine xf,
+                   const at::Tensor* scale, const at::Tensor* shift) {
+        const int64_t nidx = idx.numel();
+        TORCH_CHECK(out.numel() == nidx * v.mx_disp, "ddstore gather: shape mismatch");
+        const int out_t = dds_type_of(out);
+        TORCH_CHECK(float_out(out_t),
+                    "ddstore gather: an MX variable is fetched as f32/f16/bf16");
+        if (scale) {
+            xf.d_scale = affine_vec(*scale, v.mx_disp);
+            xf.d_shift = affine_vec(*shift, v.mx_disp);
+        }
+        ddstore::gather_rows_mx(stream(), row_dir(v), idx.data_ptr<int64_t>(), nidx,
+                                v.mx_disp, v.mx_elem, out_t, xf, out.data_ptr(), v.d_oob);
+        v.count(nidx, nidx * v.row_elems);
     }
 
     // The padded CSR gather body, `xf`, `scale` and `shift` as for

@@ -43,6 +43,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("init", &DeviceStore::init, py::call_guard<py::gil_scoped_release>())
         .def("add_csr", &DeviceStore::add_csr, py::call_guard<py::gil_scoped_release>())
         .def("init_csr", &DeviceStore::init_csr, py::call_guard<py::gil_scoped_release>())
+        .def("init_mx", &DeviceStore::init_mx, py::call_guard<py::gil_scoped_release>())
+        .def("update_mx", &DeviceStore::update_mx, py::call_guard<py::gil_scoped_release>())
         .def("ipc_handle", &DeviceStore::ipc_handle)
         .def("base_ptr", &DeviceStore::base_ptr)
         .def_static("decode_local_peer",

@@ -236,6 +236,37 @@ void graph_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_
                 int64_t nidx, int64_t ncap, int64_t ecap, int out_t, bool coo,
                 int64_t edge_fill, int64_t* d_batch, void* d_edge_out);
 
+// MX (OCP microscaling v1.0) block-scaled storage. A variable of logical
+// width `disp` keeps each row packed as
+//   [nblk * 32 element codes][nblk E8M0 scale bytes][zero pad to 16 B]
+// with nblk = ceil(disp / 32); fp8 codes take a byte, e2m1 codes a nibble
+// (even column low). The packed row is an ordinary DDS_U8 row of
+// mx_row_bytes() bytes, so everything that moves rows moves it unchanged.
+enum DDSMxElem : int { DDS_MX_E4M3 = 0, DDS_MX_E5M2 = 1, DDS_MX_E2M1 = 2 };
+inline int64_t mx_payload_bytes(int64_t disp, int elem) {
+    return (disp + 31) / 32 * (elem == DDS_MX_E2M1 ? 16 : 32);
+}
+inline int64_t mx_row_bytes(int64_t disp, int elem) {
+    return (mx_payload_bytes(disp, elem) + (disp + 31) / 32 + 15) / 16 * 16;
+}
+
+// gather_rows for an MX variable: rows of mx_row_bytes(disp, elem) bytes are
+// gathered, dequantized (code * 2^(scale byte - 127), scale byte 255 = NaN),
+// run through `xf` (affine columns are logical columns, d_scale / d_shift
+// hold `disp` floats) and cast to out_t, which must be DDS_F32, DDS_F16 or
+// DDS_BF16 (anything else launches nothing). d_out holds nidx * disp
+// elements; out-of-range indices are skipped and counted in d_oob.
+void gather_rows_mx(hipStream_t stream, const RowDir& dir, const int64_t* d_idx,
+                    int64_t nidx, int64_t disp, int elem, int out_t, const Affine& xf,
+                    void* d_out, unsigned long long* d_oob);
+
+// Quantize `nrows` rows of `disp` values (in_t DDS_F32, DDS_F16 or DDS_BF16,
+// device memory, contiguous) into packed MX rows at d_dst, by the rule in
+// docs/API.md ("MX storage"). Every byte of every packed row is written, and
+// the bytes are a pure function of the input.
+void quantize_rows_mx(hipStream_t stream, const void* d_src, int in_t, int64_t nrows,
+                      int64_t disp, int elem, void* d_dst);
+
 // Scatter rows of a packed buffer into the local shard at arbitrary local row
 // ids (inverse of gather_rows with nparts==1). Used by the epoch reshuffle to
 // place all-to-all-received rows.

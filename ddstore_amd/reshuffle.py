@@ -59,7 +59,7 @@ def reshuffle_epoch(store: DDStore, name: str, seed: int) -> None:
     prefix = torch.tensor(q["prefix"], dtype=torch.int64, device=dev)
     ntotal = int(q["nrows_total"])
     disp = int(q["disp"])
-    dtype = store._meta(name)["dtype"]
+    dtype = store._stored_dtype(name)
     size, rank = store.size, store.rank
     p0, p1 = int(q["prefix"][rank]), int(q["prefix"][rank + 1])
 
@@ -76,7 +76,7 @@ def reshuffle_epoch(store: DDStore, name: str, seed: int) -> None:
     j_send = (src_of_slot == rank).nonzero(as_tuple=True)[0]
     dest = torch.searchsorted(prefix, j_send, right=True) - 1
     send_counts = torch.bincount(dest, minlength=size).cpu().tolist()
-    sendbuf = store.get_batch(name, perm[j_send], dtype=dtype)
+    sendbuf = store._get_stored(name, perm[j_send])
 
     # --- recv side: my slots ordered by (source rank, j) to match the
     # concatenation order all_to_all delivers
@@ -249,7 +249,7 @@ def reshuffle_epoch_chunked(
     ntotal = int(q["nrows_total"])
     disp = int(q["disp"])
     itemsize = int(q["itemsize"])
-    dtype = store._meta(name)["dtype"]
+    dtype = store._stored_dtype(name)
     p0, p1 = int(q["prefix"][rank]), int(q["prefix"][rank + 1])
     row_bytes = max(disp * itemsize, 1)
 
@@ -282,7 +282,7 @@ def reshuffle_epoch_chunked(
     close_mine = (closing_slot >= p0) & (closing_slot < p1)
     my_heads = heads[close_mine]
     head_rows = (
-        store.get_batch(name, my_heads, dtype=dtype)
+        store._get_stored(name, my_heads)
         if my_heads.numel()
         else None
     )
@@ -314,7 +314,7 @@ def reshuffle_epoch_chunked(
             # closing writes take the saved head row; give them a harmless
             # in-range source slot for the batched gather, then substitute
             src = torch.where(is_close, w_mine, src)
-            buf = store.get_batch(name, src, dtype=dtype)
+            buf = store._get_stored(name, src)
             if is_close.any():
                 rows = is_close.nonzero(as_tuple=True)[0]
                 for r in rows.tolist():

@@ -32,7 +32,7 @@ from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _C
+from . import _C, mx
 from .comm import Comm, as_comm, default_device_index
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
@@ -303,8 +303,80 @@ class DDStore:
         updates from remote reads is the CALLER's job: write outside the
         epoch windows in which peers read (the fence choreography of
         vae-ddp.py:240-265 exists exactly for this)."""
+        self._refuse_mx("update", name)
         t = _as_tensor(arr)
         self._backend.update(name, self._staged(t), int(offset))
+
+    # ------------------------------------------------------------- MX storage
+    def _refuse_mx(self, what: str, name: str) -> None:
+        if "mx" in self._vars.get(name, ()):
+            raise TypeError(
+                f"ddstore {what}: '{name}' is an MX block-scaled variable; "
+                f"{what} does not support those (fill it with update_mx, read "
+                "it with get_batch)")
+
+    def init_mx(self, name: str, nrows: int, disp: int, elem: str = "e4m3") -> None:
+        """Pre-allocate a zeroed MX block-scaled variable of logical width
+        ``disp`` (collective, like :meth:`init`); fill it with
+        :meth:`update_mx`. Each row is stored packed in ``mx.row_bytes(disp,
+        elem)`` bytes -- 32 values share a power-of-two scale byte, elements
+        are ``"e4m3"``, ``"e5m2"`` or ``"e2m1"`` (docs/API.md, "MX storage").
+        Natively this is a uint8 variable of packed rows: :meth:`get`,
+        :meth:`local_shard`, :meth:`dump` and :meth:`reshuffle` see and move
+        the packed bytes, :meth:`get_batch` dequantizes."""
+        disp = int(disp)
+        if elem not in mx.ELEMS:
+            raise ValueError(f"ddstore init_mx: unknown element kind '{elem}'")
+        if disp < 1:
+            raise ValueError("ddstore init_mx: disp must be >= 1")
+        self._validate_uniform(disp, f"mx-{elem}")
+        nrows_all = self.comm.allgather(int(nrows))
+        if self.mode == "hip":
+            self._backend.init_mx(name, int(nrows), disp, mx.ELEMS.index(elem), nrows_all)
+        else:
+            self._backend.init(name, int(nrows), mx.row_bytes(disp, elem), torch.uint8,
+                               nrows_all)
+        # "disp" / "dtype" describe what a fetch returns by default; the
+        # stored row is meta["mx"]["row_bytes"] uint8
+        meta = self._mkmeta(False, torch.float32, disp, nrows_all)
+        meta["mx"] = {"elem": elem, "disp": disp, "row_bytes": mx.row_bytes(disp, elem)}
+        self._vars[name] = meta
+        self._exchange_and_open(name)
+
+    def update_mx(self, name: str, arr: ArrayLike, offset: int = 0) -> None:
+        """Quantize ``arr`` (f32/f16/bf16, ``(n, disp)``, NumPy or torch, host
+        or device) into rows ``offset ..`` of this rank's shard of an MX
+        variable. Local, like :meth:`update`. On a GPU store the quantizer is
+        a kernel; a host array is staged to the device in pieces of at most
+        ``mx.STAGE_BYTES`` source bytes (64 MiB by default), so filling a
+        near-capacity shard never needs the source on the device at once."""
+        rec = self._meta(name).get("mx")
+        if rec is None:
+            raise TypeError(f"ddstore update_mx: '{name}' is not an MX variable")
+        t = _as_tensor(arr)
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"ddstore update_mx: array must be f32/f16/bf16, got {t.dtype}")
+        t = t.reshape(-1, rec["disp"]).contiguous()
+        offset = int(offset)
+        if self.mode != "hip":
+            self._backend.update(name, mx.quantize(t, rec["elem"]), offset)
+            return
+        if t.is_cuda:
+            self._backend.update_mx(name, self._staged(t), offset)
+            return
+        step = max(1, mx.STAGE_BYTES // (rec["disp"] * t.element_size()))
+        for i in range(0, t.shape[0], step):
+            piece = t[i:i + step].to(self.device).contiguous()
+            self._backend.update_mx(name, piece, offset + i)
+
+    def add_mx(self, name: str, arr: ArrayLike, elem: str = "e4m3") -> None:
+        """:meth:`init_mx` for ``arr``'s shape, then :meth:`update_mx`
+        (collective)."""
+        t = _as_tensor(arr)
+        if t.dim() != 2:
+            raise ValueError("ddstore add_mx: array must be (n, disp)")
+        self.init_mx(name, t.shape[0], t.shape[1], elem)
+        self.update_mx(name, t)
 
     def _csr_directory(self, lens: torch.Tensor):
         """Collective: allgather per-rank sample/element counts and build the
@@ -373,6 +445,7 @@ class DDStore:
         (any contiguous run). No communication, no epoch required -- the CSR
         analog of :meth:`update`. Like the reference, separating updates from
         remote reads is the caller's job."""
+        self._refuse_mx("update_csr", name)
         meta = self._meta(name)
         if not meta["is_csr"]:
             raise ValueError(f"ddstore update_csr: '{name}' is not a CSR variable")
@@ -392,6 +465,11 @@ class DDStore:
         """The store has no bool element kind (bool is stored and moved as
         bytes 0/1), so it cannot CONVERT to bool: a bool output is a byte move
         of a variable stored as bool and refused for every other variable."""
+        if "mx" in self._meta(name) and out_dtype not in (
+                None, torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(
+                f"ddstore {what}: an MX variable is fetched as float32, float16 "
+                f"or bfloat16, not {out_dtype}")
         if out_dtype == torch.bool and self._meta(name)["dtype"] != torch.bool:
             raise TypeError(
                 f"ddstore {what}: bool output needs a variable stored as bool "
@@ -481,6 +559,15 @@ class DDStore:
                 (n, meta["disp"]), dtype=dtype or meta["dtype"], device=self.device
             )
         self._account(meta, idx)
+        if "mx" in meta and self.mode != "hip":
+            # host backend: gather the packed rows, dequantize, then affine
+            # and cast as this path does for every variable
+            x = mx.dequantize(self._get_stored(name, idx), meta["disp"], meta["mx"]["elem"])
+            if affine is not None:
+                scale, shift, _ = self._affine_operands("get_batch", name, affine)
+                x = x * scale + shift
+            out.copy_(x.to(out.dtype))
+            return out
         if affine is not None:
             scale, shift, per_col = self._affine_operands("get_batch", name, affine)
             if out.dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -506,12 +593,33 @@ class DDStore:
                 self._backend.gather(name, idx, out)
         return out
 
+    def _stored_dtype(self, name: str) -> torch.dtype:
+        """The dtype of the rows as the shard holds them (uint8 packed rows
+        for an MX variable)."""
+        meta = self._meta(name)
+        return torch.uint8 if "mx" in meta else meta["dtype"]
+
+    def _get_stored(self, name: str, idx: torch.Tensor) -> torch.Tensor:
+        """Rows as stored: :meth:`get_batch` without a cast, and the packed
+        rows of an MX variable. ``idx`` is an int64 tensor on the store
+        device."""
+        meta = self._meta(name)
+        if "mx" not in meta:
+            return self.get_batch(name, idx, dtype=meta["dtype"])
+        out = torch.empty((idx.numel(), meta["mx"]["row_bytes"]), dtype=torch.uint8,
+                          device=self.device)
+        self._backend.gather(name, idx.contiguous(), out)
+        return out
+
     def gather_into(self, name: str, idx_dev: torch.Tensor, out: torch.Tensor) -> None:
         """Minimal-overhead gather for hot loops: ``idx_dev`` must already be a
         contiguous int64 tensor on the store device and ``out`` a matching
         output tensor (as returned/validated by a prior :meth:`get_batch`).
         Skips Python-side normalization; the native layer still validates."""
         self._check_out_dtype("gather_into", name, out.dtype)
+        if self.mode != "hip" and "mx" in self._meta(name):
+            self.get_batch(name, idx_dev, out=out)  # host: dequantized in Python
+            return
         self._backend.gather(name, idx_dev, out)
 
     def get_csr(
@@ -523,6 +631,7 @@ class DDStore:
         """Gather variable-length samples; returns ``(values, offsets)`` where
         ``values[offsets[i]:offsets[i+1]]`` are sample ``indices[i]``'s
         elements (shape ``(total_elems, disp)``)."""
+        self._refuse_mx("get_csr", name)
         meta = self._meta(name)
         if not meta["is_csr"]:
             raise ValueError(f"ddstore get_csr: '{name}' is not a CSR variable")
@@ -578,6 +687,7 @@ class DDStore:
         An out-of-range index gives an all-pad row of length 0 and is counted
         in ``query()["oob_skipped"]``. On the GPU this is one kernel launch:
         no scan, no scratch, no host sync, every element written once."""
+        self._refuse_mx("get_csr_padded", name)
         meta = self._meta(name)
         if not meta["is_csr"]:
             raise ValueError(f"ddstore get_csr_padded: '{name}' is not a CSR variable")
@@ -657,6 +767,8 @@ class DDStore:
     def _graph_pair(self, node_name: str, edge_index_name: str, edge_dtype):
         """Host-side validation of a (node, edge index) pair, done once per
         pair of names; returns ``(node meta, edge meta, output dtype)``."""
+        self._refuse_mx("get_graph_batch", node_name)
+        self._refuse_mx("get_graph_batch", edge_index_name)
         nmeta, emeta = self._meta(node_name), self._meta(edge_index_name)
         if (node_name, edge_index_name) not in self._graph_pairs:
             for nm, m in ((node_name, nmeta), (edge_index_name, emeta)):
@@ -918,6 +1030,7 @@ class DDStore:
         stream (transient memory independent of the number of rows) and reads
         ``4 * disp`` numbers back with one sync; the ranks' partials are merged
         on the host. The gather counters of :meth:`query` are not touched."""
+        self._refuse_mx("column_stats", name)
         meta = self._meta(name)
         disp = meta["disp"]
         q = self._backend.query(name)
@@ -1025,6 +1138,8 @@ class DDStore:
             "size": self.size,
             "prefix": list(q["prefix"]),
         }
+        if "mx" in meta:  # the shard holds packed rows
+            payload["mx"] = dict(meta["mx"])
         if meta["is_csr"]:
             payload["goff"] = meta["goff"]
             payload["elem_prefix"] = list(q["elem_prefix"])
@@ -1049,12 +1164,24 @@ class DDStore:
                 0, dtype=torch.int64
             )
             self.add_csr(name, shard, lengths)
+        elif "mx" in payload:
+            self.init_mx(name, shard.shape[0], payload["mx"]["disp"], payload["mx"]["elem"])
+            self._backend.update(name, self._staged(shard.contiguous()), 0)
         else:
             self.add(name, shard)
 
     # ------------------------------------------------------------------- misc
     def query(self, name: str) -> dict:
-        return self._backend.query(name)
+        """Layout and counters of a variable. For an MX variable ``disp`` and
+        ``itemsize`` describe the stored uint8 rows; ``mx_elem``, ``mx_disp``
+        and ``row_bytes`` give the element kind, the logical width and the
+        packed row size, and ``bytes_gathered`` counts packed bytes."""
+        q = self._backend.query(name)
+        rec = self._meta(name).get("mx") if name in self._vars else None
+        if rec is not None:
+            q["mx_elem"], q["mx_disp"], q["row_bytes"] = (
+                rec["elem"], rec["disp"], rec["row_bytes"])
+        return q
 
     def reset_counters(self, name: str) -> None:
         """Zero a variable's skip/traffic counters (e.g. after an intentional
