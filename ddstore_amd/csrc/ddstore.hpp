@@ -519,20 +519,33 @@ public:
     // packed rows [offset, offset + n) of the local shard. Local, like update.
     void update_mx(const std::string& name, const at::Tensor& src, int64_t offset) {
         RoctxRange rr_("ddstore::update_mx");
-        DeviceVar& v = var(name);
-        TORCH_CHECK(v.mx_elem >= 0, "ddstore update_mx: not an MX variable");
-        TORCH_CHECK(src.is_contiguous() && src.device().is_cuda() &&
-                        src.device().index() == device_,
-                    "ddstore update_mx: array must be C-contiguous on the store device");
-        const int in_t = dds_type_of(src);
-        TORCH_CHECK(float_out(in_t), "ddstore update_mx: array must be f32/f16/bf16");
-        const int64_t n = src.numel() / v.mx_disp;
-        TORCH_CHECK(src.numel() == n * v.mx_disp, "ddstore update_mx: shape mismatch");
-        TORCH_CHECK(offset >= 0 && offset + n <= v.nrows_local,
-                    "ddstore update_mx: out of range");
-        ddstore::quantize_rows_mx(stream(), src.data_ptr(), in_t, n, v.mx_disp, v.mx_elem,
-                                  (char*)v.base + offset * v.row_elems);
-        HIP_CHECK(hipStreamSynchronize(stream()));  // src may go once this returns
+        quantize_into(name, src, offset, false, "ddstore update_mx");
+    }
+
+    // MX CSR variable: init_csr over elements that are packed rows of
+    // logical width `disp`, plus the record. Filled with update_csr_mx.
+    void init_csr_mx(const std::string& name, int64_t nsamples, int64_t nelems,
+                     int64_t disp, int elem, std::vector<int64_t> nsamples_all,
+                     std::vector<int64_t> nelems_all, const at::Tensor& goff_cpu) {
+        TORCH_CHECK(elem >= DDS_MX_E4M3 && elem <= DDS_MX_E2M1,
+                    "ddstore init_csr_mx: unknown element kind");
+        TORCH_CHECK(disp >= 1 && disp < (int64_t(1) << 30),
+                    "ddstore init_csr_mx: bad disp");
+        const CsrShape csr{nelems, nelems_all, goff_cpu};
+        register_var(name, "init_csr_mx", nullptr, at::kByte, mx_row_bytes(disp, elem),
+                     nsamples, nsamples_all, &csr);
+        DeviceVar& v = vars_[name];
+        v.mx_elem = elem;
+        v.mx_disp = disp;
+    }
+
+    // update_mx for an MX CSR variable: `src` holds whole elements, quantized
+    // into the local shard from LOCAL element `elem_offset` on (the Python
+    // layer translates a sample offset, as for update_elems).
+    void update_csr_mx(const std::string& name, const at::Tensor& src,
+                       int64_t elem_offset) {
+        RoctxRange rr_("ddstore::update_csr_mx");
+        quantize_into(name, src, elem_offset, true, "ddstore update_csr_mx");
     }
 
     // purely local fills (reference ddstore.hpp:181-195), see check_update
@@ -731,8 +744,27 @@ public:
         return csr_fast(v, idx, out);
     }
 
+    // gather_csr_fast for an MX CSR variable: `out` is a capacity buffer of
+    // f32/f16/bf16 and logical width, the elements arrive dequantized (and
+    // through the scalar affine if `affine`); see csr_mx_fast.
+    at::Tensor gather_csr_mx(const std::string& name, const at::Tensor& idx,
+                             at::Tensor out, bool affine, double scale, double shift) {
+        RoctxRange rr_("ddstore::gather_csr_mx");
+        return csr_mx_fast(mx_csr_var(name, idx), idx, out,
+                           Affine{affine, (float)scale, (float)shift});
+    }
+
+    // gather_csr_mx with one (scale, shift) pair per logical column.
+    at::Tensor gather_csr_mx_cols(const std::string& name, const at::Tensor& idx,
+                                  at::Tensor out, const at::Tensor& scale,
+                                  const at::Tensor& shift) {
+        RoctxRange rr_("ddstore::gather_csr_mx_cols");
+        return csr_mx_fast(mx_csr_var(name, idx), idx, out, Affine{true}, &scale, &shift);
+    }
+
     // Graph-batch fetch in one native call: the node variable exactly as
-    // gather_csr_fast fetches it, then the edge-index variable's offsets
+    // gather_csr_fast fetches it (an MX CSR node variable with a float x_out:
+    // as gather_csr_mx does), then the edge-index variable's offsets
     // (csr_offsets), its edges relabelled to the packed batch
     // (gather_csr_relabel) and the batch vector plus both tails
     // (graph_fill); all on stream(), no host reads of device data. x_out's
@@ -758,7 +790,10 @@ public:
                     "ddstore gather_graph: node and edge variables are sharded "
                     "differently");
         const int64_t nidx = idx.numel();
-        const int64_t ncap = x_out.numel() / std::max<int64_t>(nv.row_elems, 1);
+        // an MX node variable dequantizes into a float x_out of logical width
+        const bool mx_x = nv.mx_elem >= 0 && x_out.scalar_type() != at::kByte;
+        const int64_t ncap =
+            x_out.numel() / std::max<int64_t>(mx_x ? nv.mx_disp : nv.row_elems, 1);
         TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
                         batch_out.device().is_cuda() &&
                         batch_out.device().index() == device_ &&
@@ -780,7 +815,8 @@ public:
         const int64_t ecap = edge_out.numel() / 2;
         TORCH_CHECK(out_t == DDS_I64 || ncap < (int64_t(1) << 31),
                     "ddstore gather_graph: int32 node ids need Ncap < 2^31");
-        at::Tensor ptr = csr_fast(nv, idx, x_out);
+        at::Tensor ptr =
+            mx_x ? csr_mx_fast(nv, idx, x_out, Affine{}) : csr_fast(nv, idx, x_out);
         auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
         at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
         if (nidx == 0) {
@@ -1120,6 +1156,86 @@ private:
         v.count(nidx, nidx * v.row_elems);
     }
 
+    // body of update_mx (rows of a fixed-stride MX variable) and
+    // update_csr_mx (`csr`: elements of an MX CSR one), in the words of `op`
+    void quantize_into(const std::string& name, const at::Tensor& src, int64_t offset,
+                       bool csr, const char* op) {
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.mx_elem >= 0, op, ": not an MX variable");
+        TORCH_CHECK(v.is_csr == csr, op,
+                    csr ? ": not a CSR variable" : ": not supported for CSR variables");
+        TORCH_CHECK(src.is_contiguous() && src.device().is_cuda() &&
+                        src.device().index() == device_,
+                    op, ": array must be C-contiguous on the store device");
+        const int in_t = dds_type_of(src);
+        TORCH_CHECK(float_out(in_t), op, ": array must be f32/f16/bf16");
+        const int64_t n = src.numel() / v.mx_disp;
+        TORCH_CHECK(src.numel() == n * v.mx_disp, op, ": shape mismatch");
+        TORCH_CHECK(offset >= 0 && offset + n <= v.local_count(), op, ": out of range");
+        ddstore::quantize_rows_mx(stream(), src.data_ptr(), in_t, n, v.mx_disp, v.mx_elem,
+                                  (char*)v.base + offset * v.row_elems);
+        HIP_CHECK(hipStreamSynchronize(stream()));  // src may go once this returns
+    }
+
+    // the checks of a fetch that only an MX CSR variable has
+    DeviceVar& mx_csr_var(const std::string& name, const at::Tensor& idx) {
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.is_csr && v.mx_elem >= 0,
+                    "ddstore gather_csr_mx: not an MX CSR variable");
+        check_peers(v);
+        check_idx(idx);
+        return v;
+    }
+
+    // An MX CSR variable's fetch arguments: the output dtype, the per-column
+    // vectors into `xf`, the mean sample length that sizes the lane group.
+    int csr_mx_args(const DeviceVar& v, const at::Tensor& out, Affine& xf,
+                    const at::Tensor* scale, const at::Tensor* shift,
+                    int64_t& mean_len) const {
+        const int out_t = dds_type_of(out);
+        TORCH_CHECK(float_out(out_t),
+                    "ddstore gather_csr: an MX variable is fetched as f32/f16/bf16");
+        if (scale) {
+            xf.d_scale = affine_vec(*scale, v.mx_disp);
+            xf.d_shift = affine_vec(*shift, v.mx_disp);
+        }
+        const int64_t ns = std::max<int64_t>(v.nrows_total(), 1);
+        mean_len = (v.elem_prefix.back() + ns - 1) / ns;
+        return out_t;
+    }
+
+    // One-call packed fetch of an MX CSR variable: csr_offsets, then the
+    // dequantizing gather in place of the item gather. `out` is a capacity
+    // buffer of the output dtype, logical width; returns the [n+1] offsets.
+    // `v` and `idx` are checked by the caller; bytes are counted on the
+    // device, as in csr_fast.
+    at::Tensor csr_mx_fast(DeviceVar& v, const at::Tensor& idx, at::Tensor& out, Affine xf,
+                           const at::Tensor* scale = nullptr,
+                           const at::Tensor* shift = nullptr) {
+        const int64_t nidx = idx.numel();
+        check_out(out, "ddstore gather_csr: output must be a contiguous tensor on the "
+                       "store device");
+        int64_t mean_len = 0;
+        const int out_t = csr_mx_args(v, out, xf, scale, shift, mean_len);
+        auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
+        at::Tensor off = at::empty({nidx + 1}, opts);
+        if (nidx == 0) {
+            off.zero_();
+            return off;
+        }
+        auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
+        at::Tensor scratch = at::empty(
+            {(int64_t)ddstore::csr_plan_scratch_bytes(nidx)}, bopts);
+        const CsrDir dir = csr_dir(v);
+        ddstore::csr_offsets(stream(), dir, idx.data_ptr<int64_t>(), nidx,
+                             off.data_ptr<int64_t>(), scratch.data_ptr(), v.d_oob);
+        ddstore::gather_csr_mx(stream(), dir, idx.data_ptr<int64_t>(), nidx,
+                               off.data_ptr<int64_t>(), v.mx_disp, v.mx_elem, mean_len,
+                               out_t, xf, out.numel() / v.mx_disp, out.data_ptr(), v.d_oob);
+        v.count(nidx);
+        return off;
+    }
+
     // The padded CSR gather body, `xf`, `scale` and `shift` as for
     // gather_fixed. Bytes are counted on the device (DDS_CTR_ELEMS, see query).
     void padded(const std::string& name, const at::Tensor& idx, at::Tensor& out,
@@ -1133,13 +1249,26 @@ private:
         TORCH_CHECK(max_len >= 1, "ddstore gather_csr_padded: max_len must be >= 1");
         check_out(out, "ddstore gather_csr_padded: output must be a contiguous tensor "
                        "on the store device");
-        TORCH_CHECK(out.numel() == nidx * max_len * v.row_elems,
+        // an MX variable dequantizes; asked for uint8 it moves its packed
+        // elements like any u8 variable
+        const bool mx = v.mx_elem >= 0 && !(out.scalar_type() == at::kByte && !xf.on);
+        TORCH_CHECK(out.numel() == nidx * max_len * (mx ? v.mx_disp : v.row_elems),
                     "ddstore gather_csr_padded: shape mismatch");
         TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.is_contiguous() &&
                         lengths.device().is_cuda() &&
                         lengths.device().index() == device_ &&
                         lengths.numel() == nidx,
                     "ddstore gather_csr_padded: bad lengths tensor");
+        if (mx) {
+            int64_t mean_len = 0;
+            const int out_t = csr_mx_args(v, out, xf, scale, shift, mean_len);
+            ddstore::gather_csr_padded_mx(
+                stream(), csr_dir(v), idx.data_ptr<int64_t>(), nidx, v.mx_disp, v.mx_elem,
+                mean_len, max_len, out_t, xf, (uint64_t)pad_bits, out.data_ptr(),
+                lengths.data_ptr<int64_t>(), v.d_oob);
+            v.count(nidx);
+            return;
+        }
         const int out_t = dds_type_of(out);
         TORCH_CHECK(!xf.on || float_out(out_t),
                     "ddstore gather_csr_padded: affine output must be f32/f16/bf16");

@@ -45,6 +45,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("init_csr", &DeviceStore::init_csr, py::call_guard<py::gil_scoped_release>())
         .def("init_mx", &DeviceStore::init_mx, py::call_guard<py::gil_scoped_release>())
         .def("update_mx", &DeviceStore::update_mx, py::call_guard<py::gil_scoped_release>())
+        .def("init_csr_mx", &DeviceStore::init_csr_mx, py::call_guard<py::gil_scoped_release>())
+        .def("update_csr_mx", &DeviceStore::update_csr_mx, py::call_guard<py::gil_scoped_release>())
         .def("ipc_handle", &DeviceStore::ipc_handle)
         .def("base_ptr", &DeviceStore::base_ptr)
         .def_static("decode_local_peer",
@@ -62,6 +64,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("gather_csr", &DeviceStore::gather_csr, py::call_guard<py::gil_scoped_release>())
         .def("csr_lens", &DeviceStore::csr_lens, py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_fast", &DeviceStore::gather_csr_fast, py::call_guard<py::gil_scoped_release>())
+        .def("gather_csr_mx", &DeviceStore::gather_csr_mx,
+             py::arg("name"), py::arg("idx"), py::arg("out"), py::arg("affine") = false,
+             py::arg("scale") = 1.0, py::arg("shift") = 0.0,
+             py::call_guard<py::gil_scoped_release>())
+        .def("gather_csr_mx_cols", &DeviceStore::gather_csr_mx_cols,
+             py::call_guard<py::gil_scoped_release>())
         .def("gather_graph", &DeviceStore::gather_graph, py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_padded", &DeviceStore::gather_csr_padded,
              py::arg("name"), py::arg("idx"), py::arg("out"), py::arg("lengths"),

@@ -260,6 +260,40 @@ void gather_rows_mx(hipStream_t stream, const RowDir& dir, const int64_t* d_idx,
                     int64_t nidx, int64_t disp, int elem, int out_t, const Affine& xf,
                     void* d_out, unsigned long long* d_oob);
 
+// The fetches of an MX CSR variable: a CSR variable of DDS_U8 whose elements
+// are packed rows of mx_row_bytes(disp, elem) bytes (`dir` describes that
+// variable). Elements are dequantized, run through `xf` (affine columns are
+// logical columns in [0, disp)) and cast to out_t, which must be DDS_F32,
+// DDS_F16 or DDS_BF16 (anything else launches nothing), in one launch each, no
+// scratch. `mean_len` is the variable's mean sample length in elements; it
+// only sizes the lane group.
+//
+// gather_csr_mx, the packed placement: sample d_idx[s] goes to rows
+// d_out_off[s] .. d_out_off[s+1] of a (cap_elems, disp) output. d_out_off
+// must come from csr_offsets on the same stream, which has counted the bad
+// indices and ADDED the requested total to d_ctrs[DDS_CTR_ELEMS]; this is
+// gather_csr_balanced's capacity rule: a sample with L > 0 elements whose
+// slice would end past cap_elems is not written, counts once in
+// d_ctrs[DDS_CTR_CAP], and takes its L elements back out of DDS_CTR_ELEMS.
+// d_out_off is read, never clamped. So DDS_CTR_ELEMS * mx_row_bytes is the
+// packed bytes read.
+void gather_csr_mx(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+                   int64_t nidx, const int64_t* d_out_off, int64_t disp, int elem,
+                   int64_t mean_len, int out_t, const Affine& xf, int64_t cap_elems,
+                   void* d_out, unsigned long long* d_ctrs);
+
+// gather_csr_padded_mx, the padded placement, gather_csr_padded's contract:
+// sample d_idx[s] is written to row s of a dense (nidx, max_len, disp) output,
+// its first min(len, max_len) elements decoded, the rest of the row filled
+// with the raw `pad_bits` of one output element; d_lengths[s] gets the true
+// length. An out-of-range index gives an all-pad row, length 0 and one count
+// in d_ctrs[DDS_CTR_OOB]; sum(min(len, max_len)) accumulates into
+// d_ctrs[DDS_CTR_ELEMS]. Every output element is written exactly once.
+void gather_csr_padded_mx(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+                          int64_t nidx, int64_t disp, int elem, int64_t mean_len,
+                          int64_t max_len, int out_t, const Affine& xf, uint64_t pad_bits,
+                          void* d_out, int64_t* d_lengths, unsigned long long* d_ctrs);
+
 // Quantize `nrows` rows of `disp` values (in_t DDS_F32, DDS_F16 or DDS_BF16,
 // device memory, contiguous) into packed MX rows at d_dst, by the rule in
 // docs/API.md ("MX storage"). Every byte of every packed row is written, and

@@ -2427,6 +2427,262 @@ k_gather_mx_elem(const void* const* peer_base, const int64_t* gprefix, int npart
 }
 
 // ---------------------------------------------------------------------------
+// gather_csr_mx / gather_csr_padded_mx, the fetch of an MX CSR variable: each
+// CSR element (a node, a token) is one packed row, and the samples of a
+// request are gathered, dequantized, run through `xf` and cast in one launch.
+// PADDED = false writes sample s at rows out_off[s] .. out_off[s+1] of a
+// (cap, disp) output under gather_csr_balanced's capacity rule; PADDED = true
+// writes it to row s of (n, max_len, disp) under k_gather_csr_padded's
+// contract (truncate, raw pad bits, true lengths, counters by count_padded).
+//
+// Work split: a lane group of G = 8..64 lanes per sample, grid-strided, as in
+// k_gather_csr_padded and k_gather_csr_relabel. The group resolves the sample
+// once (index, range check, owner_of over the LDS directory, the two
+// offsets, source and destination base); every lane repeats the same loads,
+// which the memory system serves as broadcasts, so the groups of a wave need
+// no shuffle and may run different trip counts.
+//
+// Data movement: a sample's valid output is take * cpr consecutive 16-B
+// chunks (cpr = disp / VEC), output chunk q being element j = q / cpr, chunk
+// column c = q % cpr. A lane starts at chunk `tid` and steps by G: (j, c)
+// advance by (G / cpr, G % cpr) with one wrap, the two divides are done once
+// per thread, and j is kept as the address of the element's packed row. A
+// lane loads its chunk's 8 / 4 / 2 payload bytes and the scale byte of the
+// chunk's block (a chunk never straddles a block), kMxU chunks in flight
+// before the first convert; per-column operands load ahead of the payload.
+// Whole passes (G * kMxU chunks) run unpredicated, the last pass predicated
+// per chunk with the same code. Output: non-temporal 16-B stores. No
+// intermediate buffer, no LDS beyond the directory. The padded tail (chunks
+// take * cpr .. max_len * cpr) gets pad16 with no load.
+//
+// Group size: the host takes G = the largest power of two with G * kMxU <=
+// mean valid chunks per sample, inside 8..64, so that a mean sample fills at
+// least one whole pass. k_gather_csr_padded sizes its group by the chunks of
+// a row instead; with kMxU chunks per lane that would leave every sample
+// below 64 * kMxU chunks in the predicated pass alone. Unlike the byte-moving
+// gathers the group is not widened to the block for few long samples.
+//
+// Measured on MI355X (profiles/csr_mx_ab.txt) at the CSR bench shape widened
+// to disp = 128 (32,768 samples of 16..239 elements, 8,192 per fetch, about
+// 1.04 M elements, bf16 output, 64-lane groups): padded to max_len = 240,
+// e4m3 139 us and e2m1 103 us against 217 us for the same data stored as f32
+// through k_gather_csr_padded; packed, e4m3 94 us and e2m1 68 us against 838
+// and 1496 us for the raw uint8 variable through get_csr(out=) plus a decode
+// in torch, and 224 us for the plain f32 byte move. The group-size rule and
+// kMxU = 8 (k_gather_mx's value) were NOT swept, and nothing else was tried.
+// ---------------------------------------------------------------------------
+template <int ELEM, typename Tout, typename Xf, bool WHOLE>
+__device__ __forceinline__ void csr_mx_pass(const Xf& xf, uintptr_t& rp, uint32_t& c,
+                                            int64_t q, int64_t nch, uint32_t group,
+                                            uint32_t cpr, uint32_t row_bytes,
+                                            uint32_t scale_off, uint32_t q_g, uint32_t r_g,
+                                            VecT<Tout, 16 / sizeof(Tout)>* __restrict__ op) {
+    constexpr int VEC = 16 / sizeof(Tout);
+    constexpr int PB = mx_bytes<ELEM>(VEC);
+    constexpr int U = kMxU;
+    using Vpay = VecT<uint8_t, PB>;
+    using Vcol = VecT<float, VEC>;
+    Vpay pay[U];
+    uint8_t sb[U];
+    Vcol cs[U], ch[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (WHOLE || q + (int64_t)u * group < nch) {
+            if constexpr (Xf::kNeedsCol) {  // ahead of the payload
+                cs[u] = *reinterpret_cast<const Vcol*>(xf.scale + c * VEC);
+                ch[u] = *reinterpret_cast<const Vcol*>(xf.shift + c * VEC);
+            }
+            pay[u] = load_global<Vpay>(rp + (uintptr_t)(c * (uint32_t)PB));
+            sb[u] = *(const DDS_GLOBAL_AS uint8_t*)(rp + scale_off +
+                                                   ((c * (uint32_t)VEC) >> 5));
+        }
+        c += r_g;
+        rp += (uintptr_t)q_g * row_bytes;
+        if (c >= cpr) {
+            c -= cpr;
+            rp += row_bytes;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (WHOLE || q + (int64_t)u * group < nch) {
+            float f[VEC];
+            mx_decode<ELEM, VEC>(pay[u], sb[u], f);
+            store_out(&op[q + (int64_t)u * group], mx_xf<Tout, VEC>(xf, f, cs[u], ch[u]));
+        }
+    }
+}
+
+template <int ELEM, typename Tout, typename Xf, bool PADDED>
+__global__ void DDS_MX_KERNEL __launch_bounds__(kBlock)
+k_gather_csr_mx(const void* const* peer_base, const int64_t* sample_prefix,
+                const int64_t* elem_prefix, int nparts, const int64_t* goff,
+                const int64_t* idx, int64_t nidx, const int64_t* __restrict__ out_off,
+                int64_t limit,  // packed: cap_elems; padded: max_len
+                uint32_t cpr, uint32_t row_bytes, uint32_t scale_off, int lg_group, Xf xf,
+                dds_u32x4 pad16, Tout* __restrict__ out, int64_t* __restrict__ lengths,
+                unsigned long long* ctrs) {
+    constexpr int VEC = 16 / sizeof(Tout);
+    using Vout = VecT<Tout, VEC>;
+    __shared__ LdsDir<uintptr_t, 2> dir;
+    __shared__ unsigned long long s_acc[2 * (kBlock / 64)];
+    dir.load(peer_base, nparts, sample_prefix, elem_prefix);
+    if constexpr (PADDED) {
+        if (blockIdx.x < kPadCountBlocks)  // block-uniform
+            count_padded(dir, nparts, goff, idx, nidx, limit, s_acc, ctrs);
+    }
+    Vout vpad;
+    __builtin_memcpy(&vpad, &pad16, sizeof(Vout));
+    const uint32_t group = 1u << lg_group;
+    const uint32_t tid = threadIdx.x & (group - 1);
+    const int64_t first =
+        (int64_t)blockIdx.x * (kBlock >> lg_group) + (threadIdx.x >> lg_group);
+    const int64_t step = (int64_t)gridDim.x * (kBlock >> lg_group);
+    // the lane's walk over (element, chunk column): the only divides
+    const uint32_t q_g = group / cpr, r_g = group - q_g * cpr;
+    const uint32_t j0 = tid / cpr, c0 = tid - j0 * cpr;
+    const int64_t pass_chunks = (int64_t)group * kMxU;
+
+    for (int64_t s = first; s < nidx; s += step) {
+        const int64_t g = idx[s];
+        uintptr_t sp = 0;
+        int64_t take = 0;  // elements to decode
+        Vout* __restrict__ op = reinterpret_cast<Vout*>(out);
+        if constexpr (PADDED) op += s * limit * (int64_t)cpr;
+        if (out_of_range(dir, nparts, g)) {
+            if constexpr (PADDED) {
+                if (tid == 0) lengths[s] = 0;  // an all-pad row
+            } else {
+                continue;  // counted by k_csr_plan1, length 0 in out_off
+            }
+        } else {
+            const int p = owner_of(dir, nparts, g);
+            const int64_t e0 = goff[g];
+            const int64_t len = goff[g + 1] - e0;
+            if constexpr (PADDED) {
+                take = len < limit ? len : limit;
+                if (tid == 0) lengths[s] = len;
+            } else {
+                if (len <= 0) continue;
+                const int64_t o0 = out_off[s];
+                if (o0 < 0 || o0 + len > limit) {  // never write past the capacity
+                    if (tid == 0) {
+                        atomicAdd(ctrs + DDS_CTR_CAP, 1ull);
+                        // k_csr_plan2 added the requested total
+                        atomicAdd(ctrs + DDS_CTR_ELEMS, (unsigned long long)(-(long long)len));
+                    }
+                    continue;
+                }
+                take = len;
+                op += o0 * (int64_t)cpr;
+            }
+            sp = dir.base[p] + (uintptr_t)((e0 - dir.prefix[1][p]) * (int64_t)row_bytes);
+        }
+        const int64_t nch = take * (int64_t)cpr;
+        uintptr_t rp = sp + (uintptr_t)j0 * row_bytes;
+        uint32_t c = c0;
+        int64_t base = 0;  // group-uniform
+        for (; base + pass_chunks <= nch; base += pass_chunks)
+            csr_mx_pass<ELEM, Tout, Xf, true>(xf, rp, c, base + tid, nch, group, cpr,
+                                              row_bytes, scale_off, q_g, r_g, op);
+        if (base < nch)
+            csr_mx_pass<ELEM, Tout, Xf, false>(xf, rp, c, base + tid, nch, group, cpr,
+                                               row_bytes, scale_off, q_g, r_g, op);
+        if constexpr (PADDED) {
+            const int64_t rowch = limit * (int64_t)cpr;
+            for (int64_t q = nch + tid; q < rowch; q += group) store_out(&op[q], vpad);
+        }
+    }
+}
+
+// Element-wise fallback (VEC = 1) of the two fetches above, for a `disp` that
+// is no multiple of VEC or an output that is not 16-B aligned: the WHOLE
+// fetch runs here. Same lane groups and the same add-and-wrap walk, over
+// (element, column) with one value per lane and step; code and nibble
+// extraction as in k_gather_mx_elem; the pad is written per element. Its
+// speed has not been measured.
+template <int ELEM, typename Tout, typename Xf>
+__global__ void DDS_MX_KERNEL __launch_bounds__(kBlock)
+k_gather_csr_mx_elem(const void* const* peer_base, const int64_t* sample_prefix,
+                     const int64_t* elem_prefix, int nparts, const int64_t* goff,
+                     const int64_t* idx, int64_t nidx, const int64_t* __restrict__ out_off,
+                     bool padded, int64_t limit, uint32_t disp, uint32_t row_bytes,
+                     uint32_t scale_off, int lg_group, Xf xf, dds_u32x4 pad16,
+                     Tout* __restrict__ out, int64_t* __restrict__ lengths,
+                     unsigned long long* ctrs) {
+    __shared__ LdsDir<uintptr_t, 2> dir;
+    __shared__ unsigned long long s_acc[2 * (kBlock / 64)];
+    dir.load(peer_base, nparts, sample_prefix, elem_prefix);
+    if (padded && blockIdx.x < kPadCountBlocks)  // block-uniform
+        count_padded(dir, nparts, goff, idx, nidx, limit, s_acc, ctrs);
+    Tout pad;
+    __builtin_memcpy(&pad, &pad16, sizeof(Tout));
+    const uint32_t group = 1u << lg_group;
+    const uint32_t tid = threadIdx.x & (group - 1);
+    const int64_t first =
+        (int64_t)blockIdx.x * (kBlock >> lg_group) + (threadIdx.x >> lg_group);
+    const int64_t step = (int64_t)gridDim.x * (kBlock >> lg_group);
+    const uint32_t q_g = group / disp, r_g = group - q_g * disp;
+    const uint32_t j0 = tid / disp, c0 = tid - j0 * disp;
+
+    for (int64_t s = first; s < nidx; s += step) {
+        const int64_t g = idx[s];
+        uintptr_t sp = 0;
+        int64_t take = 0;
+        Tout* __restrict__ op = out;
+        if (padded) op += s * limit * (int64_t)disp;
+        if (out_of_range(dir, nparts, g)) {
+            if (!padded) continue;  // counted by k_csr_plan1, length 0
+            if (tid == 0) lengths[s] = 0;
+        } else {
+            const int p = owner_of(dir, nparts, g);
+            const int64_t e0 = goff[g];
+            const int64_t len = goff[g + 1] - e0;
+            if (padded) {
+                take = len < limit ? len : limit;
+                if (tid == 0) lengths[s] = len;
+            } else {
+                if (len <= 0) continue;
+                const int64_t o0 = out_off[s];
+                if (o0 < 0 || o0 + len > limit) {
+                    if (tid == 0) {
+                        atomicAdd(ctrs + DDS_CTR_CAP, 1ull);
+                        atomicAdd(ctrs + DDS_CTR_ELEMS, (unsigned long long)(-(long long)len));
+                    }
+                    continue;
+                }
+                take = len;
+                op += o0 * (int64_t)disp;
+            }
+            sp = dir.base[p] + (uintptr_t)((e0 - dir.prefix[1][p]) * (int64_t)row_bytes);
+        }
+        const int64_t nval = take * (int64_t)disp;
+        uintptr_t rp = sp + (uintptr_t)j0 * row_bytes;
+        uint32_t col = c0;
+        for (int64_t t = tid; t < nval; t += group) {
+            const DDS_GLOBAL_AS uint8_t* row = (const DDS_GLOBAL_AS uint8_t*)rp;
+            const uint32_t sb = row[scale_off + (col >> 5)];
+            uint32_t code;
+            if constexpr (ELEM == DDS_MX_E2M1) code = (row[col >> 1] >> ((col & 1) * 4)) & 0xFu;
+            else code = row[col];
+            const float f = mx_decode2<ELEM, 0>(code, mx_scale_f32(sb)).x;
+            if constexpr (Xf::kNeedsCol) op[t] = xf.template apply<Tout>(f, xf.scale[col], xf.shift[col]);
+            else op[t] = xf.template apply<Tout>(f);
+            col += r_g;
+            rp += (uintptr_t)q_g * row_bytes;
+            if (col >= disp) {
+                col -= disp;
+                rp += row_bytes;
+            }
+        }
+        if (padded) {
+            const int64_t rowv = limit * (int64_t)disp;
+            for (int64_t t = nval + tid; t < rowv; t += group) op[t] = pad;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // quantize_rows_mx, the ingest: 8 lanes per 32-element block, 4 values each
 // (f32: one 16-B load per lane when the row width and the source allow it).
 // The block maximum is the integer maximum of the |v| bit patterns over three
@@ -2564,7 +2820,93 @@ void launch_gather_mx(hipStream_t stream, const RowDir& d, const int64_t* idx, i
                        (uint32_t)scale_off, xf, out, oob);
 }
 
+// Both placements of the MX CSR fetch (`d_out_off` null: padded, `limit` =
+// max_len; else packed, `limit` = cap_elems). The lane group comes from the
+// mean valid lane steps per sample, see k_gather_csr_mx.
+template <int ELEM, typename Tout, typename Xf>
+void launch_csr_mx(hipStream_t stream, const CsrDir& d, const int64_t* idx, int64_t n,
+                   const int64_t* d_out_off, int64_t limit, int64_t disp, int64_t mean_len,
+                   Xf xf, dds_u32x4 pad16, Tout* out, int64_t* lengths,
+                   unsigned long long* ctrs) {
+    constexpr int VEC = 16 / sizeof(Tout);
+    const bool padded = d_out_off == nullptr;
+    const int64_t row_bytes = mx_row_bytes(disp, ELEM);
+    const int64_t scale_off = mx_payload_bytes(disp, ELEM);
+    const bool vec = disp % VEC == 0 && ((uintptr_t)out % 16) == 0;
+    if (padded && mean_len > limit) mean_len = limit;
+    const int64_t work = mean_len * (vec ? disp / VEC : disp);
+    int lg = 3;
+    while (lg < 6 && ((int64_t)(2 * kMxU) << lg) <= work) ++lg;
+    const int64_t gpb = kBlock >> lg;
+    const int64_t b = (n + gpb - 1) / gpb;
+    const dim3 grid((unsigned)(b < kMaxBlocks ? b : kMaxBlocks));
+    if (!vec) {
+        hipLaunchKernelGGL((k_gather_csr_mx_elem<ELEM, Tout, Xf>), grid, dim3(kBlock), 0,
+                           stream, d.d_base, d.d_sample_prefix, d.d_elem_prefix, d.nparts,
+                           d.d_goff, idx, n, d_out_off, padded, limit, (uint32_t)disp,
+                           (uint32_t)row_bytes, (uint32_t)scale_off, lg, xf, pad16, out,
+                           lengths, ctrs);
+        return;
+    }
+    auto launch = [&](auto pd) {
+        hipLaunchKernelGGL((k_gather_csr_mx<ELEM, Tout, Xf, decltype(pd)::value>), grid,
+                           dim3(kBlock), 0, stream, d.d_base, d.d_sample_prefix,
+                           d.d_elem_prefix, d.nparts, d.d_goff, idx, n, d_out_off, limit,
+                           (uint32_t)(disp / VEC), (uint32_t)row_bytes,
+                           (uint32_t)scale_off, lg, xf, pad16, out, lengths, ctrs);
+    };
+    if (padded) launch(std::true_type{});
+    else launch(std::false_type{});
+}
+
+void dispatch_csr_mx(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+                     int64_t nidx, const int64_t* d_out_off, int64_t limit, int64_t disp,
+                     int elem, int64_t mean_len, int out_t, const Affine& xf,
+                     uint64_t pad_bits, void* d_out, int64_t* d_lengths,
+                     unsigned long long* d_ctrs) {
+    // the pad's raw bits, replicated over one 16-B output chunk
+    const int osz = (int)dds_itemsize(out_t);
+    unsigned char pb[16];
+    for (int i = 0; i < 16; ++i) pb[i] = (unsigned char)(pad_bits >> (8 * (i % osz)));
+    dds_u32x4 pad16;
+    __builtin_memcpy(&pad16, pb, 16);
+    dispatch_mx_elem(elem, [&](auto e) {
+        dispatch_dtype(out_t, [&](auto to) {
+            using Tout = typename decltype(to)::type;
+            if constexpr (std::is_same_v<Tout, float> || std::is_same_v<Tout, __half> ||
+                          std::is_same_v<Tout, __hip_bfloat16>) {
+                auto launch = [&](auto x) {
+                    launch_csr_mx<decltype(e)::value, Tout>(
+                        stream, dir, d_idx, nidx, d_out_off, limit, disp, mean_len, x, pad16,
+                        (Tout*)d_out, d_lengths, d_ctrs);
+                };
+                if (!xf.on) launch(XfCast{});
+                else if (xf.d_scale) launch(XfAffineCol{xf.d_scale, xf.d_shift});
+                else launch(XfAffine{xf.scale, xf.shift});
+            }
+        });
+    });
+}
+
 }  // namespace
+
+void gather_csr_mx(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+                   int64_t nidx, const int64_t* d_out_off, int64_t disp, int elem,
+                   int64_t mean_len, int out_t, const Affine& xf, int64_t cap_elems,
+                   void* d_out, unsigned long long* d_ctrs) {
+    if (nidx == 0 || disp == 0) return;
+    dispatch_csr_mx(stream, dir, d_idx, nidx, d_out_off, cap_elems, disp, elem, mean_len,
+                    out_t, xf, 0, d_out, nullptr, d_ctrs);
+}
+
+void gather_csr_padded_mx(hipStream_t stream, const CsrDir& dir, const int64_t* d_idx,
+                          int64_t nidx, int64_t disp, int elem, int64_t mean_len,
+                          int64_t max_len, int out_t, const Affine& xf, uint64_t pad_bits,
+                          void* d_out, int64_t* d_lengths, unsigned long long* d_ctrs) {
+    if (nidx == 0 || disp == 0 || max_len == 0) return;
+    dispatch_csr_mx(stream, dir, d_idx, nidx, nullptr, max_len, disp, elem, mean_len, out_t,
+                    xf, pad_bits, d_out, d_lengths, d_ctrs);
+}
 
 void gather_rows_mx(hipStream_t stream, const RowDir& dir, const int64_t* d_idx,
                     int64_t nidx, int64_t disp, int elem, int out_t, const Affine& xf,

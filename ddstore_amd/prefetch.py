@@ -47,6 +47,8 @@ class PrefetchLoader:
     label_name : optional second variable gathered with the same indices
     depth : int           ring depth (2 = classic double buffering)
     drop_last : bool
+                          (a CSR variable takes both only if it is an MX CSR
+                          variable or with ``pad_to``)
     pad_to : optional int CSR variables only: fetch fixed-shape padded batches
                           with ``get_csr_padded(max_len=pad_to)``; each batch
                           is ``(dense, lengths)`` instead of ``(values,
@@ -100,7 +102,8 @@ class PrefetchLoader:
             if self.pad_to < 1:
                 raise ValueError("pad_to must be >= 1")
         if self.is_csr:
-            if affine is not None and self.pad_to is None:
+            if (affine is not None and self.pad_to is None
+                    and "mx" not in store._meta(name)):
                 raise ValueError("affine is not supported for CSR variables")
             if label_name is not None and store._meta(label_name)["is_csr"]:
                 raise ValueError("label variable must be fixed-stride")
@@ -134,14 +137,18 @@ class PrefetchLoader:
                                         affine=self.affine,
                                         pad_value=self.pad_value)
         elif self.is_csr:
+            meta = store._meta(self.name)
+            # an MX CSR variable dequantizes into out_dtype (and through the
+            # affine); every other one is moved as stored
+            fused = ({"dtype": self.out_dtype or meta["dtype"], "affine": self.affine}
+                     if "mx" in meta else {})
             cap = b.numel() * self._max_len
             buf = None if slot is None else slot.get("data")
             if buf is None or buf.shape[0] < cap:
-                buf = torch.empty(
-                    (cap, store._meta(self.name)["disp"]),
-                    dtype=store._meta(self.name)["dtype"], device=store.device,
-                )
-            data = store.get_csr(self.name, b, out=buf)  # (values, offsets)
+                buf = torch.empty((cap, meta["disp"]),
+                                  dtype=fused.get("dtype", meta["dtype"]),
+                                  device=store.device)
+            data = store.get_csr(self.name, b, out=buf, **fused)  # (values, offsets)
         else:
             buf = None if slot is None else slot.get("data")
             if buf is not None and buf.shape[0] != b.numel():
@@ -247,7 +254,7 @@ class GraphPrefetchLoader(PrefetchLoader):
     node_name : str         node-aligned CSR variable (features)
     edge_index_name : str   edge-aligned CSR variable, ``disp == 2``
     indices, batch_size, label_name, depth, drop_last : as PrefetchLoader
-    coo, edge_dtype, edge_fill : as get_graph_batch
+    coo, edge_dtype, edge_fill, x_dtype : as get_graph_batch
     """
 
     def __init__(
@@ -263,6 +270,7 @@ class GraphPrefetchLoader(PrefetchLoader):
         coo: bool = True,
         edge_dtype: Optional[torch.dtype] = None,
         edge_fill: int = -1,
+        x_dtype: Optional[torch.dtype] = None,
     ):
         # refuses a bad pair of variables here, not at the first batch
         _, emeta, self._edge_out_dtype = store._graph_pair(
@@ -273,6 +281,7 @@ class GraphPrefetchLoader(PrefetchLoader):
         self.coo = bool(coo)
         self.edge_dtype = edge_dtype
         self.edge_fill = edge_fill
+        self.x_dtype = x_dtype or store._meta(node_name)["dtype"]
         goff = emeta["goff"]
         self._max_edges = int((goff[1:] - goff[:-1]).max().item()) if goff.numel() > 1 else 0
 
@@ -285,14 +294,14 @@ class GraphPrefetchLoader(PrefetchLoader):
         if bufs is None or bufs[2].numel() != ncap or bufs[1].numel() != 2 * ecap:
             # first use of the slot, or a ragged final batch
             bufs = (
-                torch.empty((ncap, meta["disp"]), dtype=meta["dtype"], device=store.device),
+                torch.empty((ncap, meta["disp"]), dtype=self.x_dtype, device=store.device),
                 torch.empty(2 * ecap, dtype=self._edge_out_dtype, device=store.device),
                 torch.empty(ncap, dtype=torch.int64, device=store.device),
             )
         data = store.get_graph_batch(
             self.name, self.edge_index_name, b, x_out=bufs[0], edge_out=bufs[1],
             batch_out=bufs[2], coo=self.coo, edge_dtype=self.edge_dtype,
-            edge_fill=self.edge_fill)
+            edge_fill=self.edge_fill, x_dtype=self.x_dtype)
         if slot is not None:
             slot["data"] = bufs
         if self.label_name is None:

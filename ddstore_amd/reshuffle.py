@@ -118,7 +118,7 @@ def _reshuffle_csr(store: DDStore, name: str, seed: int) -> None:
     _check_perm_agreement(store, perm)
     mine = perm[p0:p1].contiguous()
 
-    values, _ = store.get_csr(name, mine)
+    values, _ = store._get_csr_stored(name, mine)  # an MX variable: packed rows
     goff = meta["goff_dev"] if store.mode == "hip" else meta["goff"]
     lens = (goff[mine + 1] - goff[mine]).cpu()
     if store.mode == "hip":
@@ -127,7 +127,7 @@ def _reshuffle_csr(store: DDStore, name: str, seed: int) -> None:
 
     store._backend.free_var(name)
     del store._vars[name]
-    store.add_csr(name, values, lens)
+    store._readd_csr(name, values, lens, meta.get("mx"))
 
 
 def cycle_order_device(perm: torch.Tensor):

@@ -308,12 +308,18 @@ class DDStore:
         self._backend.update(name, self._staged(t), int(offset))
 
     # ------------------------------------------------------------- MX storage
-    def _refuse_mx(self, what: str, name: str) -> None:
-        if "mx" in self._vars.get(name, ()):
-            raise TypeError(
-                f"ddstore {what}: '{name}' is an MX block-scaled variable; "
-                f"{what} does not support those (fill it with update_mx, read "
-                "it with get_batch)")
+    def _refuse_mx(self, what: str, name: str, csr_ok: bool = False) -> None:
+        """``what`` does not serve MX variables (``csr_ok``: none but MX CSR
+        ones)."""
+        meta = self._vars.get(name, ())
+        if "mx" not in meta or (csr_ok and meta["is_csr"]):
+            return
+        use = ("update_csr_mx, read it with get_csr, get_csr_padded or "
+               "get_graph_batch" if meta["is_csr"] else "update_mx, read it with get_batch")
+        raise TypeError(
+            f"ddstore {what}: '{name}' is an MX block-scaled "
+            f"{'CSR ' if meta['is_csr'] else ''}variable; {what} does not support "
+            f"those (fill it with {use})")
 
     def init_mx(self, name: str, nrows: int, disp: int, elem: str = "e4m3") -> None:
         """Pre-allocate a zeroed MX block-scaled variable of logical width
@@ -353,6 +359,9 @@ class DDStore:
         rec = self._meta(name).get("mx")
         if rec is None:
             raise TypeError(f"ddstore update_mx: '{name}' is not an MX variable")
+        if self._meta(name)["is_csr"]:
+            raise TypeError(f"ddstore update_mx: '{name}' is an MX CSR variable; "
+                            "fill it with update_csr_mx")
         t = _as_tensor(arr)
         if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise TypeError(f"ddstore update_mx: array must be f32/f16/bf16, got {t.dtype}")
@@ -450,15 +459,94 @@ class DDStore:
         if not meta["is_csr"]:
             raise ValueError(f"ddstore update_csr: '{name}' is not a CSR variable")
         v = _as_tensor(values)
-        q = self._backend.query(name)
-        p0 = int(q["prefix"][self.rank])
-        ep0 = int(q["elem_prefix"][self.rank])
-        nloc = int(q["nrows_local"])
-        offset = int(offset)
-        if not 0 <= offset <= nloc:
-            raise IndexError(f"ddstore update_csr: sample offset {offset} out of range")
-        elem_off = int(meta["goff"][p0 + offset].item()) - ep0
+        elem_off = self._csr_elem_offset("update_csr", name, int(offset))
         self._backend.update_elems(name, self._staged(v), elem_off)
+
+    # --------------------------------------------------------- MX CSR storage
+    def init_csr_mx(self, name: str, lengths: ArrayLike, disp: int,
+                    elem: str = "e4m3") -> None:
+        """:meth:`init_csr` for an MX block-scaled CSR variable (collective):
+        every CSR element (a node, a token) of logical width ``disp`` is
+        stored as one packed row of ``mx.row_bytes(disp, elem)`` bytes
+        (docs/API.md, "MX storage"). Natively this is a uint8 CSR variable of
+        that element width: :meth:`local_shard`, :meth:`dump` and
+        :meth:`reshuffle` see and move the packed bytes, :meth:`get_csr`,
+        :meth:`get_csr_padded` and :meth:`get_graph_batch` dequantize. Fill it
+        with :meth:`update_csr_mx`."""
+        disp = int(disp)
+        if elem not in mx.ELEMS:
+            raise ValueError(f"ddstore init_csr_mx: unknown element kind '{elem}'")
+        if disp < 1:
+            raise ValueError("ddstore init_csr_mx: disp must be >= 1")
+        lens = _as_tensor(lengths).to(torch.int64).cpu()
+        nsamples, nelems, nsamples_all, nelems_all, goff_t = self._csr_directory(lens)
+        self._validate_uniform(disp, f"mx-{elem}")
+        if self.mode == "hip":
+            self._backend.init_csr_mx(name, nsamples, nelems, disp, mx.ELEMS.index(elem),
+                                      nsamples_all, nelems_all, goff_t)
+        else:
+            self._backend.init_csr(name, nsamples, nelems, mx.row_bytes(disp, elem),
+                                   torch.uint8, nsamples_all, nelems_all, goff_t)
+        # as for init_mx: "disp" / "dtype" describe a fetch's default result
+        self._register_csr_meta(name, torch.float32, disp, nsamples_all, goff_t)
+        self._vars[name]["mx"] = {"elem": elem, "disp": disp,
+                                  "row_bytes": mx.row_bytes(disp, elem)}
+
+    def _csr_elem_offset(self, what: str, name: str, offset: int) -> int:
+        """Local element offset of local sample ``offset`` of a CSR variable."""
+        q = self._backend.query(name)
+        if not 0 <= offset <= int(q["nrows_local"]):
+            raise IndexError(f"ddstore {what}: sample offset {offset} out of range")
+        g = int(q["prefix"][self.rank]) + offset
+        return int(self._meta(name)["goff"][g].item()) - int(q["elem_prefix"][self.rank])
+
+    def update_csr_mx(self, name: str, values: ArrayLike, offset: int = 0) -> None:
+        """Quantize ``values`` (f32/f16/bf16, ``(n_elems, disp)``, NumPy or
+        torch, host or device) into this rank's shard of an MX CSR variable:
+        the elements of local samples ``offset, offset+1, ...``. Local, like
+        :meth:`update_csr`; staged like :meth:`update_mx`."""
+        meta = self._meta(name)
+        rec = meta.get("mx")
+        if rec is None or not meta["is_csr"]:
+            raise TypeError(f"ddstore update_csr_mx: '{name}' is not an MX CSR variable")
+        t = _as_tensor(values)
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(
+                f"ddstore update_csr_mx: values must be f32/f16/bf16, got {t.dtype}")
+        t = t.reshape(-1, rec["disp"]).contiguous()
+        elem_off = self._csr_elem_offset("update_csr_mx", name, int(offset))
+        if self.mode != "hip":
+            self._backend.update_elems(name, mx.quantize(t, rec["elem"]), elem_off)
+            return
+        if t.is_cuda:
+            self._backend.update_csr_mx(name, self._staged(t), elem_off)
+            return
+        step = max(1, mx.STAGE_BYTES // (rec["disp"] * t.element_size()))
+        for i in range(0, t.shape[0], step):
+            piece = t[i:i + step].to(self.device).contiguous()
+            self._backend.update_csr_mx(name, piece, elem_off + i)
+
+    def add_csr_mx(self, name: str, values: ArrayLike, lengths: ArrayLike,
+                   elem: str = "e4m3") -> None:
+        """:meth:`init_csr_mx` for ``values``' width, then
+        :meth:`update_csr_mx` (collective)."""
+        t = _as_tensor(values)
+        if t.dim() != 2:
+            raise ValueError("ddstore add_csr_mx: values must be (n_elems, disp)")
+        self.init_csr_mx(name, lengths, t.shape[1], elem)
+        self.update_csr_mx(name, t)
+
+    def _readd_csr(self, name: str, stored: torch.Tensor, lens: torch.Tensor,
+                   rec: Optional[dict]) -> None:
+        """Register CSR variable ``name`` from elements as the shard holds
+        them (collective): :meth:`add_csr`, or for an MX record ``rec`` the
+        packed rows put back unchanged."""
+        if rec is None:
+            self.add_csr(name, stored, lens)
+            return
+        self.init_csr_mx(name, lens, rec["disp"], rec["elem"])
+        if stored.numel():
+            self._backend.update_elems(name, self._staged(stored.contiguous()), 0)
 
     # ------------------------------------------------------------------- reads
     def _check_out_dtype(self, what: str, name: str, out_dtype) -> None:
@@ -627,16 +715,41 @@ class DDStore:
         name: str,
         indices: ArrayLike,
         out: Optional[torch.Tensor] = None,
+        dtype: Optional[torch.dtype] = None,
+        affine: Optional[Tuple[float, float]] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Gather variable-length samples; returns ``(values, offsets)`` where
         ``values[offsets[i]:offsets[i+1]]`` are sample ``indices[i]``'s
-        elements (shape ``(total_elems, disp)``)."""
-        self._refuse_mx("get_csr", name)
+        elements (shape ``(total_elems, disp)``).
+
+        An MX CSR variable (:meth:`init_csr_mx`) arrives dequantized:
+        ``values`` is of ``dtype`` (float32 by default, float16 and bfloat16
+        allowed) and logical width, run through the optional ``affine=(scale,
+        shift)`` (numbers or per-column vectors, as in :meth:`get_batch`) on
+        the way -- on the GPU one native call, and no host sync with ``out=``.
+        Every other CSR variable is moved as stored: ``affine`` or a ``dtype``
+        other than the stored one raises ``TypeError``."""
+        self._refuse_mx("get_csr", name, csr_ok=True)
         meta = self._meta(name)
         if not meta["is_csr"]:
             raise ValueError(f"ddstore get_csr: '{name}' is not a CSR variable")
         idx = torch.as_tensor(indices, dtype=torch.int64)
         idx = idx.to(self.device, non_blocking=True).contiguous()
+        if "mx" in meta:
+            return self._get_csr_mx(name, idx, out, dtype, affine)
+        if affine is not None or dtype not in (None, meta["dtype"]):
+            raise TypeError(
+                f"ddstore get_csr: '{name}' is fetched as stored ({meta['dtype']}); "
+                "a fused cast or affine needs an MX CSR variable or get_csr_padded")
+        return self._get_csr_stored(name, idx, out)
+
+    def _get_csr_stored(self, name: str, idx: torch.Tensor,
+                        out: Optional[torch.Tensor] = None):
+        """:meth:`get_csr` of the elements as the shards hold them (the packed
+        rows of an MX CSR variable). ``idx`` is an int64 tensor on the store
+        device."""
+        meta = self._meta(name)
+        width = meta["mx"]["row_bytes"] if "mx" in meta else meta["disp"]
         if self.mode == "hip" and out is not None:
             # capacity-buffer hot path: ONE native call (lens kernel ->
             # device cumsum -> gather), no host sync, no Python between stages
@@ -656,12 +769,62 @@ class DDStore:
         torch.cumsum(lens, 0, out=out_off[1:])
         if out is None:
             total = int(out_off[-1].item())
-            out = torch.empty((total, meta["disp"]), dtype=meta["dtype"], device=self.device)
+            out = torch.empty((total, width), dtype=self._stored_dtype(name),
+                              device=self.device)
         else:
-            total = out.numel() // meta["disp"]
+            total = out.numel() // width
         self._account(meta, idx)
         self._backend.gather_csr(name, idx, out_off, out, total)
         return out, out_off
+
+    def _get_csr_mx(self, name: str, idx: torch.Tensor, out, dtype, affine):
+        """:meth:`get_csr` of an MX CSR variable."""
+        meta = self._meta(name)
+        disp, elem = meta["disp"], meta["mx"]["elem"]
+        out_dtype = dtype or (out.dtype if out is not None else torch.float32)
+        self._check_out_dtype("get_csr", name, out_dtype)
+        if out is not None and (out.dtype != out_dtype or not out.is_contiguous()
+                                or out.device != self.device):
+            raise ValueError(
+                f"ddstore get_csr: out must be a contiguous {out_dtype} tensor on "
+                "the store device")
+        per_col = False
+        if affine is not None:
+            scale, shift, per_col = self._affine_operands("get_csr", name, affine)
+        if self.mode == "hip":
+            if out is None:
+                # exact size from the host offsets (a device `indices` syncs here)
+                ih, goff = idx.cpu(), meta["goff"]
+                ih = ih[(ih >= 0) & (ih < meta["nrows_total"])]
+                out = torch.empty((int((goff[ih + 1] - goff[ih]).sum()), disp),
+                                  dtype=out_dtype, device=self.device)
+            self._account(meta, idx)
+            if per_col:
+                off = self._backend.gather_csr_mx_cols(name, idx, out, scale, shift)
+            elif affine is not None:
+                off = self._backend.gather_csr_mx(name, idx, out, True, scale, shift)
+            else:
+                off = self._backend.gather_csr_mx(name, idx, out)
+            return out, off
+        # host backend: the packed elements by the byte path (into a buffer of
+        # the caller's capacity, so the same samples are kept), dequantize,
+        # then affine and cast as get_batch does
+        if out is None:
+            packed, off = self._get_csr_stored(name, idx)
+        else:
+            cap = out.numel() // disp
+            tmp = torch.zeros((cap, meta["mx"]["row_bytes"]), dtype=torch.uint8)
+            _, off = self._get_csr_stored(name, idx, tmp)
+            # offsets are monotone: the kept samples are a prefix
+            packed = tmp[:int(off[int((off[1:] <= cap).sum())])]
+        x = mx.dequantize(packed, disp, elem)
+        if affine is not None:
+            x = x * scale + shift
+        x = x.to(out_dtype)
+        if out is None:
+            return x, off
+        out.view(-1, disp)[:x.shape[0]].copy_(x)
+        return out, off
 
     def get_csr_padded(
         self,
@@ -687,7 +850,7 @@ class DDStore:
         An out-of-range index gives an all-pad row of length 0 and is counted
         in ``query()["oob_skipped"]``. On the GPU this is one kernel launch:
         no scan, no scratch, no host sync, every element written once."""
-        self._refuse_mx("get_csr_padded", name)
+        self._refuse_mx("get_csr_padded", name, csr_ok=True)
         meta = self._meta(name)
         if not meta["is_csr"]:
             raise ValueError(f"ddstore get_csr_padded: '{name}' is not a CSR variable")
@@ -744,8 +907,13 @@ class DDStore:
         off = torch.zeros(n + 1, dtype=torch.int64)
         torch.cumsum(lengths, 0, out=off[1:])
         total = int(off[-1].item())
-        vals = torch.empty((total, disp), dtype=meta["dtype"])
+        if "mx" in meta:  # the packed elements, dequantized
+            vals = torch.empty((total, meta["mx"]["row_bytes"]), dtype=torch.uint8)
+        else:
+            vals = torch.empty((total, disp), dtype=meta["dtype"])
         self._backend.gather_csr(name, idx, off, vals, total)
+        if "mx" in meta:
+            vals = mx.dequantize(vals, disp, meta["mx"]["elem"])
         pos = torch.arange(max_len, dtype=torch.int64)
         valid = pos.unsqueeze(0) < lengths.clamp(max=max_len).unsqueeze(1)
         src = (off[:-1].unsqueeze(1) + pos.unsqueeze(0)).clamp(max=max(total - 1, 0))
@@ -767,7 +935,7 @@ class DDStore:
     def _graph_pair(self, node_name: str, edge_index_name: str, edge_dtype):
         """Host-side validation of a (node, edge index) pair, done once per
         pair of names; returns ``(node meta, edge meta, output dtype)``."""
-        self._refuse_mx("get_graph_batch", node_name)
+        self._refuse_mx("get_graph_batch", node_name, csr_ok=True)
         self._refuse_mx("get_graph_batch", edge_index_name)
         nmeta, emeta = self._meta(node_name), self._meta(edge_index_name)
         if (node_name, edge_index_name) not in self._graph_pairs:
@@ -827,6 +995,7 @@ class DDStore:
         edge_fill: int = -1,
         node_extras: Sequence[str] = (),
         edge_extras: Sequence[str] = (),
+        x_dtype: Optional[torch.dtype] = None,
     ) -> GraphBatch:
         """Fetch a minibatch of whole graphs for a message-passing model:
         packed node features, the edge index relabelled to the packed batch,
@@ -882,7 +1051,14 @@ class DDStore:
         ``node_extras``/``edge_extras`` name further CSR variables with the
         same sample lengths as the node / edge-index variable; each is fetched
         with :meth:`get_csr` and the same indices and comes back as
-        ``(values, offsets)``."""
+        ``(values, offsets)``.
+
+        The node variable may be an MX CSR variable (:meth:`init_csr_mx`):
+        ``x`` is then ``get_csr(node_name, indices, out=x_out,
+        dtype=x_dtype)[0]``, dequantized to ``x_dtype`` (float32 by default)
+        inside the same native call. MX extras come back as float32; an MX
+        edge index raises ``TypeError``, and so does ``x_dtype`` for any other
+        node variable unless it names the stored dtype."""
         nmeta, emeta, out_dtype = self._graph_pair(node_name, edge_index_name,
                                                    edge_dtype)
         for nm in node_extras:
@@ -895,6 +1071,16 @@ class DDStore:
                 "ddstore get_graph_batch: pass x_out, edge_out and batch_out together")
         idx = torch.as_tensor(indices, dtype=torch.int64).flatten()
         n, disp = idx.numel(), nmeta["disp"]
+        if x_dtype is None:
+            x_dtype = x_out.dtype if "mx" in nmeta and x_out is not None else nmeta["dtype"]
+        if "mx" in nmeta:
+            self._check_out_dtype("get_graph_batch", node_name, x_dtype)
+        elif x_dtype != nmeta["dtype"]:
+            raise TypeError(
+                f"ddstore get_graph_batch: '{node_name}' is fetched as stored "
+                f"({nmeta['dtype']}); x_dtype needs an MX CSR node variable")
+        if "mx" in nmeta and x_out is not None and x_out.dtype != x_dtype:
+            raise ValueError(f"ddstore get_graph_batch: x_out must be of {x_dtype}")
         fill = int(torch.tensor([edge_fill], dtype=out_dtype).item())
         if x_out is None:
             # exact sizes from the host offsets (a device `indices` syncs here)
@@ -903,7 +1089,7 @@ class DDStore:
             gn, ge = nmeta["goff"], emeta["goff"]
             ncap = int((gn[ih + 1] - gn[ih]).sum())
             ecap = int((ge[ih + 1] - ge[ih]).sum())
-            x_out = torch.empty((ncap, disp), dtype=nmeta["dtype"], device=self.device)
+            x_out = torch.empty((ncap, disp), dtype=x_dtype, device=self.device)
             edge_out = torch.empty(2 * ecap, dtype=out_dtype, device=self.device)
             batch_out = torch.empty(ncap, dtype=torch.int64, device=self.device)
         else:
@@ -960,7 +1146,15 @@ class DDStore:
         # nodes: what get_csr(out=) does on this path (its gather skips and
         # counts bad indices and graphs that end past the capacity)
         self._account(nmeta, idx)
-        self._backend.gather_csr(node_name, idx, ptr, x_out, ncap)
+        if "mx" in nmeta:  # the packed elements, then the kept prefix dequantized
+            rec = nmeta["mx"]
+            tmp = torch.zeros((ncap, rec["row_bytes"]), dtype=torch.uint8)
+            self._backend.gather_csr(node_name, idx, ptr, tmp, ncap)
+            kept = int(ptr[int((ptr[1:] <= ncap).sum())])
+            x_out.view(-1, rec["disp"])[:kept].copy_(
+                mx.dequantize(tmp[:kept], rec["disp"], rec["elem"]).to(x_out.dtype))
+        else:
+            self._backend.gather_csr(node_name, idx, ptr, x_out, ncap)
         x = x_out
         # both offset arrays are monotone: the kept graphs are prefixes
         nodes_fit = ptr[1:] <= ncap
@@ -1163,7 +1357,7 @@ class DDStore:
             lengths = (goff[lo + 1 : hi + 1] - goff[lo:hi]) if hi > lo else torch.zeros(
                 0, dtype=torch.int64
             )
-            self.add_csr(name, shard, lengths)
+            self._readd_csr(name, shard, lengths, payload.get("mx"))
         elif "mx" in payload:
             self.init_mx(name, shard.shape[0], payload["mx"]["disp"], payload["mx"]["elem"])
             self._backend.update(name, self._staged(shard.contiguous()), 0)
