@@ -436,6 +436,31 @@ inline void strict_check(const std::string& name, int64_t oob, int64_t cap) {
 // DeviceStore
 // ===========================================================================
 
+// Fetch replica of a fixed-stride variable: the local shard cast once to the
+// dtype its fetches ask for, so that those fetches become same-dtype byte
+// moves of narrower rows (DeviceStore, "fetch replica"). At most one per
+// variable. `demand` and `refused` live until the next invalidation (drop).
+struct CastReplica {
+    int dds_t = -1;              // dtype of the replica, -1 = none
+    void* base = nullptr;
+    size_t bytes = 0;            // as allocated
+    std::vector<void*> peers;    // host copy of the base pointers, as VarMeta::peers
+    std::vector<char> opened;
+    void** d_peers = nullptr;
+    bool complete = false;       // peers open: fetches may be served from it
+    // One rank, built inside a fetch: recorded behind the cast on
+    // `ready_stream`. Until it has completed, a fetch on another stream waits
+    // for it on the device; the host never does (a host wait inside a
+    // prefetching loop stalls the training stream that the same thread feeds).
+    hipEvent_t ready = nullptr;
+    hipStream_t ready_stream = nullptr;
+    bool stale = false;          // several ranks: given up locally, memory still
+                                 // mapped by peers until the next collective drop
+    int64_t demand[DDS_NUM_TYPES] = {};  // rows fetched with a plain narrowing cast
+    unsigned refused = 0;        // bit per dtype whose build the budget refused
+    int64_t gathers = 0;         // fetches served from the replica
+};
+
 struct DeviceVar : VarMeta {
     std::vector<char> opened;    // 1 where hipIpcOpenMemHandle was used
     void** d_peers = nullptr;
@@ -444,7 +469,21 @@ struct DeviceVar : VarMeta {
     // CSR extras
     int64_t* d_elem_prefix = nullptr;
     int64_t* d_goff = nullptr;   // replicated global element offsets [ntotal+1]
+    CastReplica rep;
+    // local_shard has handed out a writable view (valid until free): the
+    // store cannot see writes through it, so it builds no replica on its own
+    // for this variable any more; prepare_fetch still does
+    bool view_out = false;
 };
+
+inline const char* replica_dtype_name(int t) {
+    switch (t) {
+        case DDS_F32: return "float32";
+        case DDS_F16: return "float16";
+        case DDS_BF16: return "bfloat16";
+        default: return "";
+    }
+}
 
 class DeviceStore {
 public:
@@ -601,30 +640,7 @@ public:
     // the libfabric handshake's 3x Allgather, common.cxx:285-302)
     void open_peers(const std::string& name, const std::vector<std::string>& handles) {
         DeviceVar& v = var(name);
-        TORCH_CHECK((int)handles.size() == nparts_, "ddstore open_peers: size mismatch");
-        v.peers.assign(nparts_, nullptr);
-        v.opened.assign(nparts_, 0);
-        for (int r = 0; r < nparts_; ++r) {
-            if (r == rank_) {
-                v.peers[r] = v.base;
-            } else if (handles[r].size() == kLocalPeerBytes) {
-                v.peers[r] = (void*)(uintptr_t)decode_local_peer(handles[r]);
-            } else {
-                TORCH_CHECK(handles[r].size() == sizeof(hipIpcMemHandle_t),
-                            "ddstore open_peers: bad handle bytes for rank ", r);
-                hipIpcMemHandle_t h;
-                std::memcpy(&h, handles[r].data(), sizeof(h));
-                void* p = nullptr;
-                hipError_t e = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
-                TORCH_CHECK(e == hipSuccess,
-                            "ddstore open_peers: hipIpcOpenMemHandle failed for peer rank ",
-                            r, " (", hipGetErrorString(e),
-                            ") -- peers must share one node/xGMI domain and "
-                            "HSA_ENABLE_IPC_MODE_LEGACY=0 must be set");
-                v.peers[r] = p;
-                v.opened[r] = 1;
-            }
-        }
+        map_peers(handles, v.base, v.peers, v.opened);
         // one device block: [peer ptrs | prefix | elem_prefix? | counters]
         size_t nb = nparts_ * sizeof(void*) + (nparts_ + 1) * 8 +
                     (v.is_csr ? (nparts_ + 1) * 8 : 0) + DDS_NCTR * 8;
@@ -643,6 +659,97 @@ public:
         }
         v.d_oob = reinterpret_cast<unsigned long long*>(tail);
         HIP_CHECK(hipMemset(v.d_oob, 0, DDS_NCTR * 8));
+    }
+
+    // ---- fetch replica -----------------------------------------------------
+    // A fixed-stride, non-MX variable may keep its local shard a second time,
+    // cast once to a narrower float dtype (CastReplica). `gather` without
+    // affine into that dtype is then served from the replicas: the same-dtype
+    // gather kernel over the replicas' base pointers and row size, the same
+    // row directory, the same counters. The shard may not change while it is
+    // fetched (the epoch contract), so the rows are the bits the casting
+    // gather writes. With one rank the store builds the replica by itself
+    // (replica_for); with several the Python layer drives the four calls
+    // below collectively: replica_build on every rank, then -- if every rank
+    // could -- an exchange of replica_handle / replica_base_ptr and
+    // replica_open, else replica_refuse.
+
+    // Allocate the replica of `name` in dtype `st` and cast the local shard
+    // into it on stream(), synchronized. False, and nothing held, where the
+    // pair is no plain narrowing cast of a fixed-stride non-MX variable or the
+    // budget refuses (remembered, see replica_budget_ok), or -- `automatic`:
+    // the build the demand asked for, not prepare_fetch -- this rank has handed
+    // out a writable view (remembered too). A live replica of another dtype
+    // must be dropped first.
+    bool replica_build(const std::string& name, at::ScalarType st, bool automatic) {
+        RoctxRange rr_("ddstore::replica_build");
+        DeviceVar& v = var(name);
+        const int out_t = dds_type_of(st);
+        if (v.is_csr || v.mx_elem >= 0 || !ddstore::cast_rows_supported(v.dds_t, out_t))
+            return false;
+        check_peers(v);
+        if (automatic && v.view_out) {
+            v.rep.refused |= 1u << out_t;
+            return false;
+        }
+        TORCH_CHECK(!v.rep.base, "ddstore replica_build: '", name,
+                    "' already has a fetch replica");
+        return build_replica(v, out_t, true);
+    }
+    py::bytes replica_handle(const std::string& name) {
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.rep.base, "ddstore replica_handle: no replica");
+        hipIpcMemHandle_t h;
+        HIP_CHECK(hipIpcGetMemHandle(&h, v.rep.base));
+        return py::bytes(reinterpret_cast<const char*>(&h), sizeof(h));
+    }
+    uint64_t replica_base_ptr(const std::string& name) {
+        return (uint64_t)(uintptr_t)var(name).rep.base;
+    }
+    // Map the peers' replicas (entries as for open_peers) and mark the
+    // replica complete.
+    void replica_open(const std::string& name, const std::vector<std::string>& handles) {
+        DeviceVar& v = var(name);
+        TORCH_CHECK(v.rep.base && !v.rep.complete, "ddstore replica_open: no replica to open");
+        open_replica(v, handles);
+    }
+    // The build of dtype `st` did not succeed on every rank: give up what
+    // this rank built and do not ask again until the next invalidation.
+    void replica_refuse(const std::string& name, at::ScalarType st) {
+        DeviceVar& v = var(name);
+        CastReplica keep = v.rep;
+        drop_replica(v);
+        std::memcpy(v.rep.demand, keep.demand, sizeof(keep.demand));
+        v.rep.refused = keep.refused | (1u << dds_type_of(st));
+    }
+    // Release the replica of `name` (or of every variable if empty) and
+    // forget demand and refusals. The caller has made sure that no rank is
+    // still fetching from it.
+    void replica_drop(const std::string& name) {
+        if (name.empty()) {
+            for (auto& kv : vars_) drop_replica(kv.second);
+        } else {
+            drop_replica(var(name));
+        }
+    }
+    // What a collective point has to settle: (name, dtype) pairs whose demand
+    // crossed the trigger on this rank, and variables whose replica this rank
+    // has given up (local_shard) while peers still map it.
+    std::pair<std::vector<std::pair<std::string, std::string>>, std::vector<std::string>>
+    replica_pending() {
+        std::vector<std::pair<std::string, std::string>> builds;
+        std::vector<std::string> drops;
+        for (auto& kv : vars_) {
+            DeviceVar& v = kv.second;
+            if (v.rep.stale) drops.push_back(kv.first);
+            if (v.rep.base || v.is_csr || v.mx_elem >= 0) continue;
+            for (int t = 0; t < DDS_NUM_TYPES; ++t)
+                if (replica_wanted(v, t)) {
+                    builds.emplace_back(kv.first, replica_dtype_name(t));
+                    break;
+                }
+        }
+        return {builds, drops};
     }
 
     void get_range(const std::string& name, int64_t start, int64_t count,
@@ -892,14 +999,35 @@ public:
         TORCH_CHECK(src.numel() == local_idx.numel() * v.row_elems,
                     "ddstore scatter_local: shape mismatch");
         check_peers(v);  // d_oob lives in the metadata block
+        // Rows move, a fetch replica ends. With one rank it goes here; with
+        // several, dropping is collective (peers map it) and the caller has
+        // done it before the first row moves, as both reshuffle forms do.
+        if (nparts_ == 1) drop_replica(v);
+        TORCH_CHECK(!v.rep.base, "ddstore scatter_local: the variable has a fetch "
+                    "replica that peers map; drop it collectively first");
         ddstore::scatter_rows_local(stream(), v.base, v.nrows_local, v.row_elems,
                                     v.dds_t, local_idx.data_ptr<int64_t>(),
                                     local_idx.numel(), src.data_ptr(), v.d_oob);
     }
 
-    // Zero-copy view of the local shard as a torch tensor (does NOT own).
-    at::Tensor local_shard(const std::string& name) {
+    // Zero-copy view of the local shard as a torch tensor (does NOT own). A
+    // `writable` view (anything but a read that ends before this returns to
+    // the user, like dump's) ends a fetch replica: dropped at once with one
+    // rank; with several this rank stops using it and the memory, which
+    // peers still map, goes at the next collective point (replica_pending).
+    // The view stays valid until free and writes through it cannot be seen,
+    // so from here on no replica is built for the variable unasked.
+    at::Tensor local_shard(const std::string& name, bool writable = true) {
         DeviceVar& v = var(name);
+        if (writable) v.view_out = true;
+        if (writable && v.rep.base) {
+            if (nparts_ == 1) {
+                drop_replica(v);
+            } else {
+                v.rep.complete = false;
+                v.rep.stale = true;
+            }
+        }
         auto opts = at::TensorOptions().dtype(v.st).device(at::kCUDA, device_);
         return at::from_blob(v.base, {v.local_count(), v.row_elems}, opts);
     }
@@ -945,6 +1073,23 @@ public:
         return d;
     }
 
+    // The fetch replica's part of DDStore.query(): the dtype of a complete
+    // replica ("" = none), the bytes it holds, the fetches served from it,
+    // and its state on this rank: "none", "building" (allocated and cast,
+    // peers not open yet), "complete" (fetches are served from it) or "stale"
+    // (given up here, still mapped by peers).
+    py::dict replica_query(const std::string& name) {
+        const DeviceVar& v = var(name);
+        py::dict d;
+        d["replica_state"] = !v.rep.base ? "none"
+                             : v.rep.stale ? "stale"
+                             : v.rep.complete ? "complete" : "building";
+        d["replica_dtype"] = replica_dtype_name(v.rep.complete ? v.rep.dds_t : -1);
+        d["replica_bytes"] = (int64_t)v.rep.bytes;
+        d["replica_gathers"] = v.rep.gathers;
+        return d;
+    }
+
     // Zero a variable's skip/stat counters (after an intentional OOB test,
     // or between bench phases).
     void reset_counters(const std::string& name) {
@@ -954,6 +1099,7 @@ public:
             HIP_CHECK(hipMemset(v.d_oob, 0, DDS_NCTR * 8));
         }
         v.n_gather = v.rows_gathered = v.bytes_gathered = 0;
+        v.rep.gathers = 0;
     }
 
     bool has(const std::string& name) const { return vars_.count(name) > 0; }
@@ -1014,8 +1160,163 @@ private:
         }
     }
 
+    // Fill `peers` / `opened` from one entry per rank: the own base, a
+    // same-process entry (decode_local_peer) or an IPC handle to open.
+    void map_peers(const std::vector<std::string>& handles, void* own_base,
+                   std::vector<void*>& peers, std::vector<char>& opened) {
+        TORCH_CHECK((int)handles.size() == nparts_, "ddstore open_peers: size mismatch");
+        peers.assign(nparts_, nullptr);
+        opened.assign(nparts_, 0);
+        for (int r = 0; r < nparts_; ++r) {
+            if (r == rank_) {
+                peers[r] = own_base;
+            } else if (handles[r].size() == kLocalPeerBytes) {
+                peers[r] = (void*)(uintptr_t)decode_local_peer(handles[r]);
+            } else {
+                TORCH_CHECK(handles[r].size() == sizeof(hipIpcMemHandle_t),
+                            "ddstore open_peers: bad handle bytes for rank ", r);
+                hipIpcMemHandle_t h;
+                std::memcpy(&h, handles[r].data(), sizeof(h));
+                void* p = nullptr;
+                hipError_t e = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
+                TORCH_CHECK(e == hipSuccess,
+                            "ddstore open_peers: hipIpcOpenMemHandle failed for peer rank ",
+                            r, " (", hipGetErrorString(e),
+                            ") -- peers must share one node/xGMI domain and "
+                            "HSA_ENABLE_IPC_MODE_LEGACY=0 must be set");
+                peers[r] = p;
+                opened[r] = 1;
+            }
+        }
+    }
+
+    // ---- fetch replica, private half ---------------------------------------
+
+    // The budget of one replica of `need` bytes: DDSTORE_CAST_REPLICA_MB
+    // where set (0 = never), else one eighth of the device memory free now --
+    // a shard that fills most of the device gets none.
+    bool replica_budget_ok(size_t need) const {
+        const char* e = std::getenv("DDSTORE_CAST_REPLICA_MB");
+        if (e && e[0]) {
+            const unsigned long long mb = std::strtoull(e, nullptr, 10);
+            return mb > 0 && need <= (size_t)mb << 20;
+        }
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+        return need <= free_b / 8;
+    }
+
+    // Demand rule. `demand[t]` counts the rows fetched with the plain
+    // narrowing cast to t since the last invalidation; the trigger is one
+    // shard's worth, the local row count. By then the conversion has been
+    // paid in full once already, so the build (read the shard once, write
+    // half of it: 6 B per f32 element for bf16) repeats a cost the user has
+    // just accepted, and every later row saves a third of its traffic (4 + 2
+    // B per element become 2 + 2): the build is recovered within about three
+    // further epochs of such fetching. A refused build is not asked for again.
+    static bool replica_wanted(const DeviceVar& v, int t) {
+        return !v.view_out && v.nrows_local > 0 && v.rep.demand[t] >= v.nrows_local &&
+               !(v.rep.refused >> t & 1);
+    }
+
+    // `host_sync`: return with the replica finished (peers in other processes
+    // will read it); else leave `ready` behind the cast (see CastReplica).
+    bool build_replica(DeviceVar& v, int out_t, bool host_sync) {
+        CastReplica& r = v.rep;
+        const int64_t n = v.nrows_local * v.row_elems;
+        const size_t need = (size_t)(n * dds_itemsize(out_t));
+        hipError_t e = hipSetDevice(device_);
+        TORCH_CHECK(e == hipSuccess, "ddstore: hipSetDevice failed");
+        void* p = nullptr;
+        const size_t bytes = need < 256 ? 256 : need;  // as alloc_base
+        if (!replica_budget_ok(need) || hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();  // a failed hipMalloc is a refusal, no error
+            r.refused |= 1u << out_t;
+            return false;
+        }
+        r.base = p;
+        r.bytes = bytes;
+        r.dds_t = out_t;
+        ddstore::cast_rows(stream(), v.base, r.base, n, v.dds_t, out_t);
+        // other streams (the prefetcher's side streams) must find it finished
+        if (host_sync) {
+            HIP_CHECK(hipStreamSynchronize(stream()));
+        } else {
+            HIP_CHECK(hipEventCreateWithFlags(&r.ready, hipEventDisableTiming));
+            r.ready_stream = stream();
+            HIP_CHECK(hipEventRecord(r.ready, r.ready_stream));
+        }
+        return true;
+    }
+
+    void open_replica(DeviceVar& v, const std::vector<std::string>& handles) {
+        CastReplica& r = v.rep;
+        map_peers(handles, r.base, r.peers, r.opened);
+        HIP_CHECK(hipMalloc((void**)&r.d_peers, nparts_ * sizeof(void*)));
+        HIP_CHECK(hipMemcpy(r.d_peers, r.peers.data(), nparts_ * sizeof(void*),
+                            hipMemcpyHostToDevice));
+        r.complete = true;
+    }
+
+    // Invalidation: free the replica (after a device synchronize: a fetch
+    // from it may still run), close peer mappings as release() closes the
+    // shards', forget demand and refusals.
+    void drop_replica(DeviceVar& v) {
+        CastReplica& r = v.rep;
+        if (r.base) {
+            (void)hipDeviceSynchronize();
+            for (size_t k = 0; k < r.peers.size(); ++k)
+                if (r.opened[k] && r.peers[k]) (void)hipIpcCloseMemHandle(r.peers[k]);
+            if (r.d_peers) (void)hipFree(r.d_peers);
+            (void)hipFree(r.base);
+            if (r.ready) (void)hipEventDestroy(r.ready);
+        }
+        const int64_t gathers = r.gathers;
+        r = CastReplica{};
+        r.gathers = gathers;
+    }
+
+    // Whether this cast fetch of `nidx` rows into dtype `out_t` is served from
+    // the replica; counts the demand, and with one rank builds the replica in
+    // the call that crosses the trigger (several ranks: replica_pending).
+    bool replica_for(DeviceVar& v, int out_t, int64_t nidx) {
+        CastReplica& r = v.rep;
+        if (r.complete) {
+            if (r.dds_t != out_t) return false;
+            if (r.ready) replica_await(r, false);
+            return true;
+        }
+        if (v.mx_elem >= 0 || !ddstore::cast_rows_supported(v.dds_t, out_t)) return false;
+        r.demand[out_t] += nidx;
+        if (nparts_ != 1 || r.base || !replica_wanted(v, out_t)) return false;
+        if (!build_replica(v, out_t, false)) return false;
+        open_replica(v, {std::string()});
+        return true;
+    }
+
+    // Order work on stream() behind the build's cast while `ready` is
+    // pending: on the device, or (`host`) by waiting here.
+    void replica_await(CastReplica& r, bool host) {
+        if (host) {
+            HIP_CHECK(hipEventSynchronize(r.ready));
+        } else if (hipEventQuery(r.ready) != hipSuccess) {
+            (void)hipGetLastError();  // not ready is no error
+            if (stream() != r.ready_stream)
+                HIP_CHECK(hipStreamWaitEvent(stream(), r.ready, 0));
+            return;
+        }
+        (void)hipEventDestroy(r.ready);
+        r.ready = nullptr;
+    }
+
+    // The replicas' row directory: their base pointers, the variable's rows.
+    RowDir replica_dir(const DeviceVar& v) const {
+        return {v.rep.d_peers, v.d_prefix, v.rep.peers.data(), v.prefix.data(), nparts_};
+    }
+
     void release(DeviceVar& v) {
         if (!v.base) return;
+        drop_replica(v);
         for (int r = 0; r < (int)v.peers.size(); ++r)
             if (v.opened.size() > (size_t)r && v.opened[r] && v.peers[r])
                 (void)hipIpcCloseMemHandle(v.peers[r]);
@@ -1061,6 +1362,18 @@ private:
     void fill(const std::string& name, const at::Tensor& src, int64_t offset, bool elems) {
         DeviceVar& v = var(name);
         ingest(v.base, src, check_update(v, elems, src, offset, false));
+        if (v.rep.base) {
+            if (v.rep.ready) replica_await(v.rep, true);
+            // re-cast exactly the rows written, behind the master write
+            const int64_t e0 = offset * v.row_elems;
+            ddstore::cast_rows(stream(), (const char*)v.base + e0 * v.itemsize,
+                               (char*)v.rep.base + e0 * dds_itemsize(v.rep.dds_t),
+                               src.numel(), v.dds_t, v.rep.dds_t);
+            // as ingest does for the master: a fetch on another stream (the
+            // prefetcher's) after update returns must find the replica's
+            // rows as new as the shard's
+            HIP_CHECK(hipStreamSynchronize(stream()));
+        }
     }
 
     // The only places that spell a variable's directory for the launchers
@@ -1133,9 +1446,16 @@ private:
             xf.d_scale = affine_vec(*scale, v.row_elems);
             xf.d_shift = affine_vec(*shift, v.row_elems);
         }
-        ddstore::gather_rows(stream(), row_dir(v), idx.data_ptr<int64_t>(), nidx,
-                             v.row_elems, v.dds_t, out_t, xf, out.data_ptr(), v.d_oob);
-        v.count(nidx, nidx * v.row_elems * v.itemsize);
+        if (!xf.on && out_t != v.dds_t && replica_for(v, out_t, nidx)) {
+            // the same rows, already cast: a byte move from the replicas
+            ddstore::gather_rows(stream(), replica_dir(v), idx.data_ptr<int64_t>(), nidx,
+                                 v.row_elems, out_t, out_t, xf, out.data_ptr(), v.d_oob);
+            v.rep.gathers += 1;
+        } else {
+            ddstore::gather_rows(stream(), row_dir(v), idx.data_ptr<int64_t>(), nidx,
+                                 v.row_elems, v.dds_t, out_t, xf, out.data_ptr(), v.d_oob);
+        }
+        v.count(nidx, nidx * v.row_elems * v.itemsize);  // stored-dtype bytes
     }
 
     // gather_fixed for an MX variable: logical width, float outputs only,

@@ -54,6 +54,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                         return DeviceStore::decode_local_peer(std::string(entry));
                     })
         .def("open_peers", &DeviceStore::open_peers)
+        .def("replica_build", &DeviceStore::replica_build,
+             py::call_guard<py::gil_scoped_release>())
+        .def("replica_handle", &DeviceStore::replica_handle)
+        .def("replica_base_ptr", &DeviceStore::replica_base_ptr)
+        .def("replica_open", &DeviceStore::replica_open)
+        .def("replica_refuse", &DeviceStore::replica_refuse)
+        .def("replica_drop", &DeviceStore::replica_drop)
+        .def("replica_pending", &DeviceStore::replica_pending)
+        .def("replica_query", &DeviceStore::replica_query)
         .def("update", &DeviceStore::update, py::call_guard<py::gil_scoped_release>())
         .def("update_elems", &DeviceStore::update_elems, py::call_guard<py::gil_scoped_release>())
         .def("reset_counters", &DeviceStore::reset_counters)
@@ -83,7 +92,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("column_stats", &DeviceStore::column_stats,
              py::call_guard<py::gil_scoped_release>())
         .def("scatter_local", &DeviceStore::scatter_local, py::call_guard<py::gil_scoped_release>())
-        .def("local_shard", &DeviceStore::local_shard)
+        .def("local_shard", &DeviceStore::local_shard, py::arg("name"),
+             py::arg("writable") = true)
         .def("epoch_begin", &DeviceStore::epoch_begin, py::call_guard<py::gil_scoped_release>())
         .def("epoch_end", &DeviceStore::epoch_end, py::call_guard<py::gil_scoped_release>())
         .def("epoch_active", &DeviceStore::epoch_active)

@@ -301,6 +301,16 @@ void gather_csr_padded_mx(hipStream_t stream, const CsrDir& dir, const int64_t* 
 void quantize_rows_mx(hipStream_t stream, const void* d_src, int in_t, int64_t nrows,
                       int64_t disp, int elem, void* d_dst);
 
+// Dense narrowing cast of `n_elems` contiguous elements, d_dst[i] =
+// cast(d_src[i]) by the rule the casting gathers use (docs/API.md, cast
+// semantics; f64 -> f16/bf16 rounds through f32). Supported pairs
+// (cast_rows_supported): DDS_F64 -> DDS_F32 / DDS_F16 / DDS_BF16 and DDS_F32
+// -> DDS_F16 / DDS_BF16; any other pair launches nothing. Both pointers are
+// device memory aligned to their element; one launch on `stream`.
+bool cast_rows_supported(int in_t, int out_t);
+void cast_rows(hipStream_t stream, const void* d_src, void* d_dst, int64_t n_elems,
+               int in_t, int out_t);
+
 // Scatter rows of a packed buffer into the local shard at arbitrary local row
 // ids (inverse of gather_rows with nparts==1). Used by the epoch reshuffle to
 // place all-to-all-received rows.

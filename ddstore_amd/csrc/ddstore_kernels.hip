@@ -2951,4 +2951,75 @@ void quantize_rows_mx(hipStream_t stream, const void* d_src, int in_t, int64_t n
     });
 }
 
+// ===========================================================================
+// Dense narrowing cast (the fetch replica of DeviceStore): dst[i] =
+// cvt<Tout>(src[i]), the conversion XfCast applies inside the gathers, so a
+// replica row holds exactly the bits a casting fetch of that row would write.
+// Grid-stride; the body moves 16 B of output per lane (the store-width rule at
+// k_gather_oneshot), and the same lanes convert the `head` elements before the
+// first 16-B boundary of dst and the `n - head - body * VEC` elements behind
+// the last whole chunk one by one. No f32 arithmetic; DDS_MX_KERNEL is the same
+// precaution for new code as above.
+// ===========================================================================
+namespace {
+
+template <typename Tin, typename Tout>
+__global__ void DDS_MX_KERNEL __launch_bounds__(kBlock)
+k_cast_rows(const Tin* __restrict__ src, Tout* __restrict__ dst, int64_t n, int64_t head,
+            int64_t body) {
+    constexpr int VEC = 16 / sizeof(Tout);
+    const int64_t t0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = t0; t < body; t += step) {
+        const VecT<Tin, VEC> vin =
+            *reinterpret_cast<const VecT<Tin, VEC>*>(src + head + t * VEC);
+        VecT<Tout, VEC> vout;
+        xf_chunk<Tout, VEC, true>(XfCast{}, nullptr, nullptr, vin, vout, 0u);
+        *reinterpret_cast<VecT<Tout, VEC>*>(dst + head + t * VEC) = vout;
+    }
+    const int64_t edge = n - body * VEC;  // head + tail elements
+    for (int64_t t = t0; t < edge; t += step) {
+        const int64_t i = t < head ? t : t + body * VEC;
+        dst[i] = cvt<Tout>(src[i]);
+    }
+}
+
+} // namespace
+
+bool cast_rows_supported(int in_t, int out_t) {
+    if (in_t == DDS_F64) return out_t == DDS_F32 || out_t == DDS_F16 || out_t == DDS_BF16;
+    if (in_t == DDS_F32) return out_t == DDS_F16 || out_t == DDS_BF16;
+    return false;
+}
+
+void cast_rows(hipStream_t stream, const void* d_src, void* d_dst, int64_t n_elems,
+               int in_t, int out_t) {
+    if (n_elems <= 0 || !cast_rows_supported(in_t, out_t)) return;
+    dispatch_dtype(in_t, [&](auto ti) {
+        dispatch_dtype(out_t, [&](auto to) {
+            using Tin = typename decltype(ti)::type;
+            using Tout = typename decltype(to)::type;
+            if constexpr ((std::is_same_v<Tin, double> || std::is_same_v<Tin, float>) &&
+                          sizeof(Tout) < sizeof(Tin) &&
+                          (std::is_same_v<Tout, float> || std::is_same_v<Tout, __half> ||
+                           std::is_same_v<Tout, __hip_bfloat16>)) {
+                constexpr int VEC = 16 / sizeof(Tout);
+                // elements up to dst's first 16-B boundary; the body needs src
+                // aligned to its own vector there, else everything is an edge
+                int64_t head =
+                    (int64_t)((16 - (uintptr_t)d_dst % 16) % 16) / (int64_t)sizeof(Tout);
+                if (head > n_elems) head = n_elems;
+                const Tin* src = (const Tin*)d_src;
+                const bool vec_ok = (uintptr_t)d_dst % sizeof(Tout) == 0 &&
+                                    (uintptr_t)(src + head) % (VEC * sizeof(Tin)) == 0;
+                const int64_t body = vec_ok ? (n_elems - head) / VEC : 0;
+                const int64_t work = body > 0 ? body : n_elems;
+                hipLaunchKernelGGL((k_cast_rows<Tin, Tout>), dim3(n_blocks(work)),
+                                   dim3(kBlock), 0, stream, src, (Tout*)d_dst, n_elems,
+                                   head, body);
+            }
+        });
+    });
+}
+
 } // namespace ddstore

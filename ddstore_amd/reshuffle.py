@@ -52,6 +52,7 @@ def reshuffle_epoch(store: DDStore, name: str, seed: int) -> None:
             "ddstore reshuffle: cannot move data inside an open epoch "
             "(concurrent gets would race); call epoch_end() first"
         )
+    store._end_replica(name)  # rows move: a fetch replica ends here
     q = store.query(name)
     if q["is_csr"]:
         return _reshuffle_csr(store, name, seed)
@@ -236,6 +237,9 @@ def reshuffle_epoch_chunked(
             "ddstore reshuffle: cannot move data inside an open epoch "
             "(concurrent gets would race); call epoch_end() first"
         )
+    # collective and up front: a rank that writes no row in any chunk
+    # must not keep a directory of replicas its peers have freed
+    store._end_replica(name)
     q = store.query(name)
     if q["is_csr"]:
         raise ValueError(

@@ -1183,7 +1183,16 @@ class DDStore:
 
     def local_shard(self, name: str) -> torch.Tensor:
         """Zero-copy view of this rank's shard (rows x disp). Valid until
-        ``free``."""
+        ``free``.
+
+        The view is writable and the store cannot see writes through it, so on
+        the GPU backend this call ends the variable's fetch replica
+        (:meth:`prepare_fetch`) -- with several ranks for this rank at once
+        and for all at the next :meth:`epoch_begin`, :meth:`prepare_fetch` or
+        :meth:`drop_fetch_replica` -- and the store builds none for the
+        variable by itself afterwards. A replica built later by
+        :meth:`prepare_fetch` does not follow writes through a view taken
+        earlier: call it again after writing."""
         return self._backend.local_shard(name)
 
     # -------------------------------------------------------------- statistics
@@ -1272,7 +1281,124 @@ class DDStore:
         """Collective epoch fence (reference MPI_Win_fence, ddstore.cxx:51-63):
         local stream fence + barrier; throws on double-begin."""
         self._backend.epoch_begin()
+        if self.mode == "hip" and self.size > 1:
+            self._settle_replicas()
         self.comm.barrier()
+
+    # ---------------------------------------------------------- fetch replicas
+    def _replica_info(self, name: str) -> dict:
+        """The fetch replica's part of :meth:`query`: ``replica_dtype`` (name
+        of the dtype fetches are served in, ``""`` = none), ``replica_bytes``,
+        ``replica_gathers`` and ``replica_state`` -- this rank's ``"none"``,
+        ``"building"``, ``"complete"`` or ``"stale"`` (given up here through
+        :meth:`local_shard`, still mapped by peers). The host backend has no
+        fused cast and so no replica."""
+        if self.mode == "hip":
+            return dict(self._backend.replica_query(name))
+        return {"replica_state": "none", "replica_dtype": "", "replica_bytes": 0,
+                "replica_gathers": 0}
+
+    def _replica_states(self, name: str) -> list:
+        """Collective: every rank's ``(replica_state, replica_dtype)`` of
+        ``name``. One rank's state can differ from its peers' (a ``stale``
+        replica), so whatever enters further collectives decides from this
+        list, never from the local state."""
+        info = self._replica_info(name)
+        return self.comm.allgather((info["replica_state"], info["replica_dtype"]))
+
+    def _settle_replicas(self) -> None:
+        """Several ranks: a fetch replica must be readable by peers and opening
+        peer memory is collective, so what single ranks have come to want (the
+        demand trigger) or given up (:meth:`local_shard`) is settled here --
+        one small allgather, and work only where some rank has something
+        pending."""
+        builds, drops = self._backend.replica_pending()
+        every = self.comm.allgather((builds, drops))
+        drop = sorted({n for _, d in every for n in d})
+        if drop:
+            self._drop_replicas(drop)
+        for name, dt in sorted({(n, t) for b, _ in every for n, t in b}):
+            if all(st == "none" for st, _ in self._replica_states(name)):
+                self._build_replica(name, getattr(torch, dt), automatic=True)
+
+    def _drop_replicas(self, names) -> None:
+        """Collective: nobody may still be fetching from a peer's replica when
+        its owner frees it."""
+        torch.cuda.synchronize(self.device)
+        self.comm.barrier()
+        for n in names:
+            self._backend.replica_drop(n)
+        self.comm.barrier()
+
+    def _end_replica(self, name: str) -> None:
+        """Collective, before rows of ``name`` move (the reshuffles): drop its
+        fetch replica if any rank holds one. A CSR or MX variable never does;
+        for the others this costs one small allgather."""
+        meta = self._vars.get(name)  # unknown: the caller's own check raises
+        if self.mode != "hip" or meta is None or meta["is_csr"] or "mx" in meta:
+            return
+        if any(st != "none" for st, _ in self._replica_states(name)):
+            self._drop_replicas([name])
+
+    def _build_replica(self, name: str, dtype: torch.dtype,
+                       automatic: bool = False) -> bool:
+        """Collective, all or nothing, for a variable no rank holds a replica
+        of: every rank casts its shard, the ranks exchange handles as
+        :meth:`_exchange_and_open` does for shards, and only then is the
+        replica used. One rank that refuses (its budget; for an ``automatic``
+        build also a view it has handed out) refuses it for all."""
+        ok = bool(self._backend.replica_build(name, dtype, automatic))
+        if not all(self.comm.allgather(ok)):
+            self._backend.replica_refuse(name, dtype)
+            return False
+        if self.size > 1 and getattr(self.comm, "same_process", False) is True:
+            h = struct.pack("=qQ", os.getpid(), self._backend.replica_base_ptr(name))
+        else:
+            h = self._backend.replica_handle(name) if self.size > 1 else b""
+        self._backend.replica_open(name, self.comm.allgather(h))
+        self.comm.barrier()
+        return True
+
+    def prepare_fetch(self, name: str, dtype: torch.dtype) -> bool:
+        """Build the fetch replica of ``name`` for fetches into ``dtype`` now
+        (collective): every rank keeps its shard a second time, cast once to
+        ``dtype``, and ``get_batch`` / ``gather_into`` calls that ask for
+        ``dtype`` without ``affine`` become byte moves of the narrower rows
+        with bit-identical results. Without this call the store builds the
+        replica by itself once a rank has fetched one shard's worth of rows
+        that way (one rank: inside that fetch; several: at the next
+        :meth:`epoch_begin`) -- unless :meth:`local_shard` has handed out a
+        view of the variable. Returns whether a replica of ``dtype`` is in
+        place: ``False`` where the pair is no narrowing float cast (f64 ->
+        f32/f16/bf16, f32 -> f16/bf16) of a fixed-stride variable, where the
+        budget refuses (docs/API.md, "Fetch replicas") and on the host
+        backend. A replica of another dtype, or one that a rank has given up
+        through :meth:`local_shard`, is dropped on every rank and rebuilt.
+
+        A replica is a copy: rows written through a :meth:`local_shard` view
+        after this call are not in it. Call ``prepare_fetch`` (or
+        :meth:`drop_fetch_replica`) again after such writes; :meth:`update`
+        needs nothing."""
+        meta = self._meta(name)
+        if self.mode != "hip" or meta["is_csr"] or "mx" in meta:
+            return False
+        states = self._replica_states(name)
+        if all(st == "complete" and dt and getattr(torch, dt) == dtype
+               for st, dt in states):
+            return True
+        if any(st != "none" for st, _ in states):
+            self._drop_replicas([name])
+        return self._build_replica(name, dtype)
+
+    def drop_fetch_replica(self, name: Optional[str] = None) -> None:
+        """Release the fetch replica of ``name``, or of every variable
+        (collective). Fetches go back to the casting kernel; demand is counted
+        afresh."""
+        if self.mode != "hip":
+            return
+        if name is not None:
+            self._meta(name)
+        self._drop_replicas([name or ""])
 
     def epoch_end(self) -> None:
         self._backend.epoch_end()
@@ -1324,7 +1450,9 @@ class DDStore:
         meta = self._meta(name)
         q = self._backend.query(name)
         payload = {
-            "shard": self._backend.local_shard(name).cpu().clone(),
+            # read and gone: not a view a user could write through
+            "shard": (self._backend.local_shard(name, False) if self.mode == "hip"
+                      else self._backend.local_shard(name)).cpu().clone(),
             "disp": meta["disp"],
             "dtype": str(meta["dtype"]),
             "is_csr": meta["is_csr"],
@@ -1371,6 +1499,7 @@ class DDStore:
         and ``row_bytes`` give the element kind, the logical width and the
         packed row size, and ``bytes_gathered`` counts packed bytes."""
         q = self._backend.query(name)
+        q.update(self._replica_info(name))
         rec = self._meta(name).get("mx") if name in self._vars else None
         if rec is not None:
             q["mx_elem"], q["mx_disp"], q["row_bytes"] = (
@@ -1393,6 +1522,7 @@ class DDStore:
         out = {}
         for name in list(self._vars):
             q = self._backend.query(name)
+            q.update(self._replica_info(name))
             out[name] = {
                 k: q[k]
                 for k in (
@@ -1401,6 +1531,10 @@ class DDStore:
                     "bytes_gathered",
                     "oob_skipped",
                     "cap_skipped",
+                    "replica_state",
+                    "replica_dtype",
+                    "replica_bytes",
+                    "replica_gathers",
                 )
                 if k in q
             }
