@@ -949,6 +949,104 @@ public:
         return {ptr, edge_ptr};
     }
 
+    // Radius-graph fetch in one native call: the position variable (plain
+    // CSR, 3 columns of f32 or f64) exactly as gather_csr_fast fetches it,
+    // then the edges built from the packed positions by the rule in
+    // ddstore_kernels.h (radius_count, radius_fill) and the batch vector plus
+    // both tails (graph_fill); all on stream(). pos_out's capacity in nodes is
+    // Ncap and batch_out holds exactly Ncap int64; edge_out holds 2 * Ecap
+    // ids, int64 or int32, and vec_out, if edge_vec, 3 * Ecap f32. With
+    // size_edges the two edge buffers are allocated here, of exactly the
+    // counted edges (edge_out only gives the dtype): the ONE path that reads
+    // device data on the host, edge_ptr[n] between count and fill. Returns
+    // (ptr, edge_ptr, edge_out, vec_out); edge_ptr is [n+1], counts 0 edges
+    // for a graph whose nodes were not kept and is otherwise unclamped. Every
+    // element of batch_out and edge_out is written; vec_out only on rows of
+    // kept edges.
+    std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gather_radius_graph(
+        const std::string& pos_name, const at::Tensor& idx, double r,
+        int64_t max_neighbors, bool loop, at::Tensor pos_out, at::Tensor edge_out,
+        at::Tensor batch_out, at::Tensor vec_out, bool edge_vec, bool size_edges,
+        bool coo, int64_t edge_fill) {
+        RoctxRange rr_("ddstore::gather_radius_graph");
+        DeviceVar& pv = var(pos_name);
+        TORCH_CHECK(pv.is_csr, "ddstore gather_radius_graph: not a CSR variable");
+        check_peers(pv);
+        check_idx(idx);
+        TORCH_CHECK(pv.mx_elem < 0 && pv.row_elems == 3 &&
+                        (pv.dds_t == DDS_F32 || pv.dds_t == DDS_F64),
+                    "ddstore gather_radius_graph: positions must be a plain f32/f64 "
+                    "CSR variable with disp == 3");
+        const float rf = (float)r;
+        TORCH_CHECK(std::isfinite(rf) && rf > 0.0f,
+                    "ddstore gather_radius_graph: r must be positive and finite");
+        const float r2 = rf * rf;
+        const int64_t nidx = idx.numel();
+        const int64_t ncap = pos_out.numel() / 3;
+        TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
+                        batch_out.device().is_cuda() &&
+                        batch_out.device().index() == device_ &&
+                        batch_out.numel() == ncap,
+                    "ddstore gather_radius_graph: batch_out must be a contiguous "
+                    "int64 tensor of pos_out's capacity on the store device");
+        TORCH_CHECK(edge_out.scalar_type() == at::kLong ||
+                        edge_out.scalar_type() == at::kInt,
+                    "ddstore gather_radius_graph: edge ids are int64 or int32");
+        const int out_t = dds_type_of(edge_out);
+        TORCH_CHECK(out_t == DDS_I64 || ncap < (int64_t(1) << 31),
+                    "ddstore gather_radius_graph: int32 node ids need Ncap < 2^31");
+        at::Tensor ptr = csr_fast(pv, idx, pos_out);
+        auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
+        auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
+        at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
+        at::Tensor scratch = at::empty(
+            {(int64_t)ddstore::radius_scratch_bytes(nidx, ncap)}, bopts);
+        if (nidx == 0) {
+            edge_ptr.zero_();
+        } else {
+            ddstore::radius_count(stream(), pos_out.data_ptr(), pv.dds_t,
+                                  ptr.data_ptr<int64_t>(), nidx, ncap, r2, max_neighbors,
+                                  loop, scratch.data_ptr(), edge_ptr.data_ptr<int64_t>());
+        }
+        if (size_edges) {
+            const int64_t total = nidx ? edge_ptr[nidx].item<int64_t>() : 0;  // syncs
+            edge_out = at::empty({2 * total}, edge_out.options());
+            if (edge_vec)
+                vec_out = at::empty({total, 3}, edge_out.options().dtype(at::kFloat));
+        }
+        TORCH_CHECK(edge_out.is_contiguous() && edge_out.device().is_cuda() &&
+                        edge_out.device().index() == device_ &&
+                        edge_out.numel() % 2 == 0,
+                    "ddstore gather_radius_graph: edge_out must be a contiguous "
+                    "tensor of 2 * Ecap ids on the store device");
+        const int64_t ecap = edge_out.numel() / 2;
+        TORCH_CHECK((uintptr_t)edge_out.data_ptr() % dds_itemsize(out_t) == 0 &&
+                        (uintptr_t)batch_out.data_ptr() % 8 == 0,
+                    "ddstore gather_radius_graph: misaligned output");
+        float* d_vec = nullptr;
+        if (edge_vec) {
+            TORCH_CHECK(vec_out.scalar_type() == at::kFloat && vec_out.is_contiguous() &&
+                            vec_out.device().is_cuda() &&
+                            vec_out.device().index() == device_ &&
+                            vec_out.numel() == 3 * ecap,
+                        "ddstore gather_radius_graph: vec_out must be a contiguous "
+                        "float32 tensor of 3 * Ecap elements on the store device");
+            // never nullptr, which would switch the vectors off: with ecap == 0
+            // nothing is written through it
+            d_vec = ecap ? vec_out.data_ptr<float>() : nullptr;
+        }
+        if (nidx > 0)
+            ddstore::radius_fill(stream(), pos_out.data_ptr(), pv.dds_t,
+                                 ptr.data_ptr<int64_t>(), edge_ptr.data_ptr<int64_t>(),
+                                 nidx, ncap, ecap, r2, loop, scratch.data_ptr(), out_t,
+                                 coo, edge_out.data_ptr(), d_vec);
+        ddstore::graph_fill(stream(), ptr.data_ptr<int64_t>(),
+                            edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, out_t, coo,
+                            edge_fill, batch_out.data_ptr<int64_t>(),
+                            edge_out.data_ptr());
+        return {ptr, edge_ptr, edge_out, vec_out};
+    }
+
     // Padded CSR fetch: one launch writes the dense (n, max_len, disp)
     // batch (cast / affine fused, pad broadcast from `pad_bits`, the raw
     // bits of one output element) and the true per-sample lengths. The

@@ -32,6 +32,7 @@ using ddstore::HostStore;
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "ddstore_amd native core (MI355X / gfx950)";
     m.attr("MAX_PARTS") = DDS_MAX_PARTS;
+    m.attr("RADIUS_TILE") = ddstore::radius_tile_nodes();
     m.def("cycle_order", &ddstore::cycle_order,
           py::call_guard<py::gil_scoped_release>(),
           "Concatenated-cycle traversal of a permutation (order, starts)");
@@ -80,6 +81,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("gather_csr_mx_cols", &DeviceStore::gather_csr_mx_cols,
              py::call_guard<py::gil_scoped_release>())
         .def("gather_graph", &DeviceStore::gather_graph, py::call_guard<py::gil_scoped_release>())
+        .def("gather_radius_graph", &DeviceStore::gather_radius_graph,
+             py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_padded", &DeviceStore::gather_csr_padded,
              py::arg("name"), py::arg("idx"), py::arg("out"), py::arg("lengths"),
              py::arg("max_len"), py::arg("pad_bits"), py::arg("affine") = false,

@@ -236,6 +236,47 @@ void graph_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_
                 int64_t nidx, int64_t ncap, int64_t ecap, int out_t, bool coo,
                 int64_t edge_fill, int64_t* d_batch, void* d_edge_out);
 
+// Radius-graph fetch (DeviceStore::gather_radius_graph): the edges of a batch
+// of graphs built from their node positions. d_pos holds the packed positions
+// of the request, (ncap, 3) of pos_t (DDS_F32 or DDS_F64; anything else
+// launches nothing), as gather_csr_balanced has just written them on the same
+// stream, and d_ptr its [nidx+1] offsets: local, contiguous memory, so neither
+// launcher needs an owner directory. Each coordinate is taken as f32 (f64
+// rounds to nearest even); for nodes i, j of one graph d = pos[i] - pos[j] per
+// coordinate, d2 = (dx*dx + dy*dy) + dz*dz in f32 without contraction, and
+// (src = i, dst = j) is an edge iff d2 <= r2 and (i != j or loop). A graph's
+// edges are ordered by dst, then src; with max_neighbors = K > 0 every dst
+// keeps its first K sources in that order (K <= 0: all).
+//
+// radius_count: d_edge_ptr[0..nidx] = exclusive scan of the per-graph edge
+// counts, where a graph with d_ptr[s+1] > ncap (its positions were not
+// fetched) and an empty one count 0; never clamped by any edge capacity. It
+// leaves the per-node degrees in d_scratch for radius_fill. Two launches.
+// d_scratch: radius_scratch_bytes(nidx, ncap) bytes, no zeroing needed.
+//
+// radius_fill: the edges of every graph with d_ptr[s+1] <= ncap and
+// d_edge_ptr[s+1] <= ecap, edge e at column d_edge_ptr[s] + e of a (2, ecap)
+// output of out_t (DDS_I64 or DDS_I32; coo) or at that row of an (ecap, 2)
+// one, both ids shifted by d_ptr[s]; with d_vec_out != nullptr row
+// d_edge_ptr[s] + e of that (ecap, 3) f32 array is (dx, dy, dz). d_scratch and
+// every other argument are radius_count's, on the same stream. Slots of no
+// kept edge are left to graph_fill (edge index) or untouched (vectors). One
+// launch; no atomics and no counters in either.
+//
+// radius_tile_nodes: the nodes one LDS slice holds; larger graphs stream
+// through it (a second code path, for tests to aim at).
+int radius_tile_nodes();
+size_t radius_scratch_bytes(int64_t nidx, int64_t ncap);
+void radius_count(hipStream_t stream, const void* d_pos, int pos_t,
+                  const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r2,
+                  int64_t max_neighbors, bool loop, void* d_scratch,
+                  int64_t* d_edge_ptr);
+void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                 const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                 int64_t ncap, int64_t ecap, float r2, bool loop,
+                 const void* d_scratch, int out_t, bool coo, void* d_edge_out,
+                 float* d_vec_out);
+
 // MX (OCP microscaling v1.0) block-scaled storage. A variable of logical
 // width `disp` keeps each row packed as
 //   [nblk * 32 element codes][nblk E8M0 scale bytes][zero pad to 16 B]

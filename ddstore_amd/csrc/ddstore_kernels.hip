@@ -1303,6 +1303,331 @@ k_graph_fill(const int64_t* __restrict__ ptr, const int64_t* __restrict__ edge_p
 }
 
 // ---------------------------------------------------------------------------
+// Radius-graph fetch: the edges of a batch of graphs built from the node
+// positions the CSR gather has just packed into the caller's buffer, instead
+// of being stored and moved. Three kernels between that gather and
+// k_graph_fill (which writes the batch vector and both tails, unchanged):
+//   k_radius_count   per-node degree (capped at K) and per-graph edge count
+//   k_radius_scan    edge_ptr = exclusive scan of the per-graph counts
+//   k_radius_fill    the kept graphs' edges, relabelled, and the edge vectors
+// The membership rule is exact and the same in both passes (docs/API.md,
+// "Radius graphs"): d2 = (dx*dx + dy*dy) + dz*dz in f32 with contraction off,
+// edge iff d2 <= r2 and (src != dst or loop). No MFMA: the inner dimension is
+// 3, and the |a|^2 + |b|^2 - 2ab form would lose the rule to cancellation.
+//
+// Mapping, both passes: GROUP lanes per graph on a persistent grid. The group
+// stages the graph's positions in its own LDS slice as f32 x[], y[], z[]
+// (kRadiusTile nodes, 3 KiB, converted once), every lane keeps up to
+// kRadiusCentres centres (dst nodes lane, lane + GROUP, ...) in registers,
+// and all lanes walk the sources in step: one LDS address per group and
+// instruction, a broadcast. Each source read serves every centre of the lane,
+// so a graph of up to kRadiusCentres * GROUP nodes (256 at GROUP = 64: every
+// graph of the 16..239-node bench shape) costs three LDS reads per source
+// once, not once per centre round. A graph with more nodes than a slice
+// streams its sources through the slice tile by tile while the centres keep
+// their running counts, and one with more centres than a pass repeats the
+// walk for the next block of centres; the positions come from L2 again.
+// A lane group is a wave or part of one, so the staging is ordered by a
+// wavefront fence and no block barrier: the groups of a block run graphs of
+// different sizes independently.
+//
+// Small graphs: several graphs share a wave. GROUP is 16 when the request
+// averages under 48 nodes per graph (ncap / nidx) and 64 otherwise; at 16 a
+// wave walks four graphs at once, their slices kRadiusPad dwords apart so the
+// four broadcast addresses fall in different banks. Sixteen slices are 49 KiB
+// of static LDS, three blocks per CU, which the grid cap follows. Splitting a
+// centre's source range over lanes instead was not tried.
+//
+// The fill pass reads the degrees the count pass left in scratch (an int32
+// per node) rather than counting again: a centre's first edge is edge_ptr[s]
+// plus the exclusive scan of the degrees in front of it, a wave scan per
+// block of centres. A lane then writes its centre's run directly, 8-B (4-B)
+// stores that are scattered across the lanes of one instruction and
+// contiguous per lane; staging a graph's edges in LDS to flush them as
+// coalesced 16-B stores was not tried. A lane never writes more edges than
+// its centre's degree, so the run stays inside what the scan reserved.
+//
+// Measured on MI355X (profiles/radius_graph_ab.txt), 8,192 graphs of 16..239
+// nodes, f32, r = 1.0 at 4.5 nodes per unit volume, 1.04 M nodes, 13.25 M
+// edges, int64 ids, exact capacities: the whole fetch 498 us (707 us with edge
+// vectors) against 182 us for get_graph_batch moving the same edges stored as
+// int64 (17x the positions' bytes) and 10.2 ms for get_csr plus a torch
+// construction. Per kernel: count 90 us, scan 10 us, fill 343 us (207 us into
+// the (Ecap, 2) layout, one 16-B store per edge), k_graph_fill 35 us. Both
+// passes do the same 166 M pair tests, so the fill is bound by its scattered
+// stores. GROUP = 16 forced at this shape: 814 us. The slice size,
+// kRadiusCentres and the grids were chosen by construction and not swept.
+// ---------------------------------------------------------------------------
+
+// v_pk_*_f32 stay out of these kernels: the rule is one rounding per
+// operation, written out scalar.
+#define DDS_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+constexpr int kRadiusTile = 256;    // nodes per LDS slice
+constexpr int kRadiusPad = 8;       // dwords between the slices of a block
+constexpr int kRadiusCentres = 4;   // centres a lane keeps in registers
+constexpr int kRadiusSlice = 3 * kRadiusTile + kRadiusPad;
+constexpr int kRadiusScanPer = 8;   // counts per thread and scan round
+
+// Orders the LDS stores of a lane group before its loads (and its loads
+// before the next stores). The group never spans waves, a wave issues its LDS
+// operations in order, so this only has to hold the compiler.
+__device__ __forceinline__ void group_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One coordinate by the store's cast rule: f64 rounds to nearest even.
+template <typename Tin>
+__device__ __forceinline__ float radius_coord(Tin v) {
+    if constexpr (std::is_same_v<Tin, double>) return f64_to_f32(v);
+    else return v;
+}
+
+// Nodes [0, tn) of `p` (3 coordinates each) into the slice: consecutive
+// lanes read consecutive coordinates.
+template <typename Tin, int GROUP>
+__device__ __forceinline__ void radius_stage(float* sl, const Tin* __restrict__ p,
+                                             int tn, int tid) {
+    for (int e = tid; e < 3 * tn; e += GROUP) {
+        const int node = e / 3;
+        sl[(e - 3 * node) * kRadiusTile + node] = radius_coord(p[e]);
+    }
+}
+
+// The centres of one pass: centre c of the lane is node cb + c * GROUP + tid
+// of the graph, a NaN position (which is nobody's neighbour) past its end.
+template <typename Tin, int GROUP>
+struct RadiusCentres {
+    float x[kRadiusCentres], y[kRadiusCentres], z[kRadiusCentres];
+    int64_t j[kRadiusCentres];
+
+    __device__ __forceinline__ void load(const Tin* __restrict__ gp, int64_t n,
+                                         int64_t cb, int tid) {
+#pragma unroll
+        for (int c = 0; c < kRadiusCentres; ++c) {
+            j[c] = cb + c * GROUP + tid;
+            const bool in = j[c] < n;
+            x[c] = in ? radius_coord(gp[3 * j[c]]) : __builtin_nanf("");
+            y[c] = in ? radius_coord(gp[3 * j[c] + 1]) : 0.0f;
+            z[c] = in ? radius_coord(gp[3 * j[c] + 2]) : 0.0f;
+        }
+    }
+};
+
+// Sources [0, tn) of the slice against the first R centres of the lane;
+// hit(c, i, dx, dy, dz) for every edge (src = slice node i, dst = centre c),
+// sources ascending. self[c] is the centre's own slot in the slice, or -1.
+template <int R, typename C, typename Hit>
+__device__ __forceinline__ void radius_walk(const float* sl, int tn, const C& ctr,
+                                            const int (&self)[kRadiusCentres],
+                                            float r2, bool loop, Hit&& hit) {
+#pragma clang fp contract(off)
+    for (int i = 0; i < tn; ++i) {
+        const float sx = sl[i], sy = sl[kRadiusTile + i], sz = sl[2 * kRadiusTile + i];
+#pragma unroll
+        for (int c = 0; c < R; ++c) {
+            const float dx = sx - ctr.x[c], dy = sy - ctr.y[c], dz = sz - ctr.z[c];
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 <= r2 && (loop || i != self[c])) hit(c, i, dx, dy, dz);
+        }
+    }
+}
+
+// All sources of graph `gp` (n nodes) against the centres of one pass, tile
+// by tile; a graph of one tile was staged by the caller (`staged`).
+// hit(c, src, dx, dy, dz) with src the node's index in the graph.
+template <typename Tin, int GROUP, typename Hit>
+__device__ __forceinline__ void radius_pass(float* sl, const Tin* __restrict__ gp,
+                                            int64_t n, bool staged,
+                                            const RadiusCentres<Tin, GROUP>& ctr,
+                                            int64_t cb, int tid, float r2, bool loop,
+                                            Hit&& hit) {
+    // centres in use: the same number in every lane of the group
+    const int64_t left = (n - cb + GROUP - 1) / GROUP;
+    const int nr = left < kRadiusCentres ? (int)left : kRadiusCentres;
+    for (int64_t t0 = 0; t0 < n; t0 += kRadiusTile) {
+        const int tn = n - t0 < kRadiusTile ? (int)(n - t0) : kRadiusTile;
+        if (!staged) {
+            group_lds_sync();  // the walk of the tile before is done
+            radius_stage<Tin, GROUP>(sl, gp + 3 * t0, tn, tid);
+            group_lds_sync();
+        }
+        int self[kRadiusCentres];
+#pragma unroll
+        for (int c = 0; c < kRadiusCentres; ++c) {
+            const int64_t d = ctr.j[c] - t0;
+            self[c] = d >= 0 && d < tn ? (int)d : -1;
+        }
+        auto at = [&](int c, int i, float dx, float dy, float dz) {
+            hit(c, t0 + i, dx, dy, dz);
+        };
+        switch (nr) {
+            case 1: radius_walk<1>(sl, tn, ctr, self, r2, loop, at); break;
+            case 2: radius_walk<2>(sl, tn, ctr, self, r2, loop, at); break;
+            case 3: radius_walk<3>(sl, tn, ctr, self, r2, loop, at); break;
+            default: radius_walk<4>(sl, tn, ctr, self, r2, loop, at); break;
+        }
+    }
+}
+static_assert(kRadiusCentres == 4, "radius_pass dispatches 1..4 centres");
+
+// Degrees and per-graph counts. deg[ptr[s] + j] = min(neighbours of node j of
+// graph s, kcap) for every graph whose nodes were kept (ptr[s+1] <= ncap);
+// counts[s] = their sum, 0 for every other graph (its positions were never
+// fetched). Every counts[s] is written; deg only for kept nodes.
+template <typename Tin, int GROUP>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_radius_count(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
+               int64_t nidx, int64_t ncap, float r2, int kcap, bool loop,
+               int64_t* __restrict__ counts, int32_t* __restrict__ deg) {
+    constexpr int GPB = kBlock / GROUP;
+    __shared__ float s_pos[GPB * kRadiusSlice];
+    float* sl = s_pos + (threadIdx.x / GROUP) * kRadiusSlice;
+    const int tid = threadIdx.x % GROUP;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        const int64_t n = p1 - p0;
+        int64_t total = 0;
+        if (n > 0 && p0 >= 0 && p1 <= ncap) {
+            const Tin* __restrict__ gp = pos + 3 * p0;
+            const bool staged = n <= kRadiusTile;
+            if (staged) {
+                group_lds_sync();  // the graph before is done with the slice
+                radius_stage<Tin, GROUP>(sl, gp, (int)n, tid);
+                group_lds_sync();
+            }
+            for (int64_t cb = 0; cb < n; cb += kRadiusCentres * GROUP) {
+                RadiusCentres<Tin, GROUP> ctr;
+                ctr.load(gp, n, cb, tid);
+                int cnt[kRadiusCentres] = {0, 0, 0, 0};
+                radius_pass<Tin, GROUP>(sl, gp, n, staged, ctr, cb, tid, r2, loop,
+                                        [&](int c, int64_t, float, float, float) {
+                                            ++cnt[c];
+                                        });
+#pragma unroll
+                for (int c = 0; c < kRadiusCentres; ++c) {
+                    if (ctr.j[c] < n) {
+                        const int d = cnt[c] < kcap ? cnt[c] : kcap;
+                        deg[p0 + ctr.j[c]] = d;
+                        total += d;
+                    }
+                }
+            }
+        }
+        for (int off = GROUP / 2; off > 0; off >>= 1) total += __shfl_xor(total, off, GROUP);
+        if (tid == 0) counts[s] = total;
+    }
+}
+
+// edge_ptr[0..nidx] = exclusive scan of counts[0..nidx), ONE block: every
+// thread sums kRadiusScanPer consecutive counts, the block scans the sums,
+// and a running carry joins the rounds (2048 graphs each). A round is a few
+// microseconds against the O(nodes^2) pass in front of it, so the tile
+// aggregates and second launch of the CSR plan are not worth having here.
+__global__ void __launch_bounds__(kBlock)
+k_radius_scan(const int64_t* __restrict__ counts, int64_t nidx,
+              int64_t* __restrict__ edge_ptr) {
+    __shared__ int64_t s_wsum2[2 * (kBlock / 64)];
+    __shared__ int64_t s_tot[2];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    int64_t carry = 0;
+    if (threadIdx.x == 0) edge_ptr[0] = 0;
+    for (int64_t base = 0; base < nidx; base += (int64_t)kBlock * kRadiusScanPer) {
+        const int64_t i0 = base + (int64_t)threadIdx.x * kRadiusScanPer;
+        int64_t v[kRadiusScanPer];
+        int64_t x = 0, y = 0;
+#pragma unroll
+        for (int k = 0; k < kRadiusScanPer; ++k) {
+            v[k] = i0 + k < nidx ? counts[i0 + k] : 0;
+            x += v[k];
+        }
+        const int64_t mine = x;
+        block_scan_pair(x, y, s_wsum2, lane, wave, s_tot);
+        int64_t run = carry + x - mine;
+#pragma unroll
+        for (int k = 0; k < kRadiusScanPer; ++k) {
+            run += v[k];
+            if (i0 + k < nidx) edge_ptr[i0 + k + 1] = run;
+        }
+        carry += s_tot[0];
+        __syncthreads();  // LDS reused next round
+    }
+}
+
+// The edges of every graph with ptr[s+1] <= ncap and edge_ptr[s+1] <= ecap:
+// edge e of the graph (dst ascending, then src ascending, each dst cut at its
+// degree) at column edge_ptr[s] + e of a (2, ecap) output (COO) or at that row
+// of an (ecap, 2) one, both ids shifted by ptr[s]; with VEC row edge_ptr[s] + e
+// of vec is (dx, dy, dz) = pos[src] - pos[dst]. Nothing else is written: the
+// tail of the edge index is k_graph_fill's.
+template <typename Tin, typename Tout, int GROUP, bool COO, bool VEC>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_radius_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
+              const int64_t* __restrict__ edge_ptr, int64_t nidx, int64_t ncap,
+              int64_t ecap, float r2, bool loop, const int32_t* __restrict__ deg,
+              Tout* __restrict__ out, float* __restrict__ vec) {
+    constexpr int GPB = kBlock / GROUP;
+    __shared__ float s_pos[GPB * kRadiusSlice];
+    float* sl = s_pos + (threadIdx.x / GROUP) * kRadiusSlice;
+    const int tid = threadIdx.x % GROUP;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        const int64_t e0 = edge_ptr[s], e1 = edge_ptr[s + 1];
+        const int64_t n = p1 - p0;
+        if (n <= 0 || p0 < 0 || p1 > ncap || e1 <= e0 || e0 < 0 || e1 > ecap) continue;
+        const Tin* __restrict__ gp = pos + 3 * p0;
+        const bool staged = n <= kRadiusTile;
+        if (staged) {
+            group_lds_sync();
+            radius_stage<Tin, GROUP>(sl, gp, (int)n, tid);
+            group_lds_sync();
+        }
+        int64_t carry = e0;  // first edge slot of the next centre
+        for (int64_t cb = 0; cb < n; cb += kRadiusCentres * GROUP) {
+            RadiusCentres<Tin, GROUP> ctr;
+            ctr.load(gp, n, cb, tid);
+            int d[kRadiusCentres], w[kRadiusCentres] = {0, 0, 0, 0};
+            int64_t start[kRadiusCentres];
+#pragma unroll
+            for (int c = 0; c < kRadiusCentres; ++c) {
+                d[c] = ctr.j[c] < n ? deg[p0 + ctr.j[c]] : 0;
+                int incl = d[c];
+                for (int off = 1; off < GROUP; off <<= 1) {
+                    const int a = __shfl_up(incl, off, GROUP);
+                    if (tid >= off) incl += a;
+                }
+                start[c] = carry + (incl - d[c]);
+                carry += __shfl(incl, GROUP - 1, GROUP);
+            }
+            radius_pass<Tin, GROUP>(
+                sl, gp, n, staged, ctr, cb, tid, r2, loop,
+                [&](int c, int64_t src, float dx, float dy, float dz) {
+                    if (w[c] >= d[c]) return;  // the K cap, and the reserved run
+                    const int64_t o = start[c] + w[c]++;
+                    const Tout a = static_cast<Tout>(src + p0);
+                    const Tout b = static_cast<Tout>(ctr.j[c] + p0);
+                    if constexpr (COO) {
+                        out[o] = a;
+                        out[ecap + o] = b;
+                    } else {
+                        reinterpret_cast<IdPair<Tout>*>(out)[o] = IdPair<Tout>{a, b};
+                    }
+                    if constexpr (VEC) {
+                        vec[3 * o] = dx;
+                        vec[3 * o + 1] = dy;
+                        vec[3 * o + 2] = dz;
+                    }
+                });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Local scatter (reshuffle placement): row r of src -> local row
 // local_idx[r] of base. Same chunk mapping as gather.
 // ---------------------------------------------------------------------------
@@ -2123,6 +2448,95 @@ void graph_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_
         hipLaunchKernelGGL((k_graph_fill<int32_t, G>), dim3(grid), dim3(kBlock), 0,
                            stream, d_ptr, d_edge_ptr, nidx, ncap, ecap, coo,
                            (int32_t)edge_fill, d_batch, (int32_t*)d_edge_out);
+}
+
+int radius_tile_nodes() { return kRadiusTile; }
+
+size_t radius_scratch_bytes(int64_t nidx, int64_t ncap) {
+    return (size_t)(nidx + 1) * 8 + (size_t)(ncap + 1) * 4;
+}
+
+namespace {
+
+// Lanes per graph of the radius kernels (see the section note); the
+// environment override is for A/B runs.
+int radius_group(int64_t nidx, int64_t ncap) {
+    static const int forced = [] {
+        const char* e = getenv("DDSTORE_RADIUS_GROUP");
+        const int v = e ? atoi(e) : 0;
+        return (v == 16 || v == 64) ? v : 0;
+    }();
+    if (forced) return forced;
+    return ncap / (nidx > 0 ? nidx : 1) < 48 ? 16 : 64;
+}
+
+// Persistent grid of the radius kernels: every wave slot the LDS slices leave
+// (8 blocks per CU at 64 lanes per graph, 3 at 16), never more than the work.
+int radius_grid(int64_t nidx, int group) {
+    const int64_t b = (nidx + (kBlock / group) - 1) / (kBlock / group);
+    const int64_t cap = (int64_t)cu_count() * (group == 64 ? kBlocksPerCU : 3);
+    return (int)(b < cap ? b : cap);
+}
+
+}  // namespace
+
+void radius_count(hipStream_t stream, const void* d_pos, int pos_t,
+                  const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r2,
+                  int64_t max_neighbors, bool loop, void* d_scratch,
+                  int64_t* d_edge_ptr) {
+    if (nidx == 0) return;
+    int64_t* counts = reinterpret_cast<int64_t*>(d_scratch);
+    int32_t* deg = reinterpret_cast<int32_t*>(counts + nidx + 1);
+    const int kcap = max_neighbors > 0 && max_neighbors < INT32_MAX
+                         ? (int)max_neighbors : INT32_MAX;
+    const int group = radius_group(nidx, ncap);
+    const int grid = radius_grid(nidx, group);
+    auto launch = [&](auto ti, auto G) {
+        using Tin = typename decltype(ti)::type;
+        hipLaunchKernelGGL((k_radius_count<Tin, G()>), dim3(grid), dim3(kBlock), 0,
+                           stream, (const Tin*)d_pos, d_ptr, nidx, ncap, r2, kcap,
+                           loop, counts, deg);
+    };
+    dispatch_group<16, 64>(group, [&](auto G) {
+        if (pos_t == DDS_F64) launch(TypeTag<double>{}, G);
+        else if (pos_t == DDS_F32) launch(TypeTag<float>{}, G);
+    });
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, counts, nidx,
+                       d_edge_ptr);
+}
+
+void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                 const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                 int64_t ncap, int64_t ecap, float r2, bool loop,
+                 const void* d_scratch, int out_t, bool coo, void* d_edge_out,
+                 float* d_vec_out) {
+    if (nidx == 0 || ecap == 0) return;
+    const int32_t* deg = reinterpret_cast<const int32_t*>(
+        reinterpret_cast<const int64_t*>(d_scratch) + nidx + 1);
+    const int group = radius_group(nidx, ncap);
+    const int grid = radius_grid(nidx, group);
+    auto launch = [&](auto ti, auto to, auto G, auto c, auto v) {
+        using Tin = typename decltype(ti)::type;
+        using Tout = typename decltype(to)::type;
+        hipLaunchKernelGGL(
+            (k_radius_fill<Tin, Tout, G(), decltype(c)::value, decltype(v)::value>),
+            dim3(grid), dim3(kBlock), 0, stream, (const Tin*)d_pos, d_ptr, d_edge_ptr,
+            nidx, ncap, ecap, r2, loop, deg, (Tout*)d_edge_out, d_vec_out);
+    };
+    auto launch_flags = [&](auto ti, auto to, auto G) {
+        if (coo && d_vec_out) launch(ti, to, G, std::true_type{}, std::true_type{});
+        else if (coo) launch(ti, to, G, std::true_type{}, std::false_type{});
+        else if (d_vec_out) launch(ti, to, G, std::false_type{}, std::true_type{});
+        else launch(ti, to, G, std::false_type{}, std::false_type{});
+    };
+    auto launch_out = [&](auto ti, auto G) {
+        if (out_t == DDS_I64) launch_flags(ti, TypeTag<int64_t>{}, G);
+        else if (out_t == DDS_I32) launch_flags(ti, TypeTag<int32_t>{}, G);
+    };
+    dispatch_group<16, 64>(group, [&](auto G) {
+        if (pos_t == DDS_F64) launch_out(TypeTag<double>{}, G);
+        else if (pos_t == DDS_F32) launch_out(TypeTag<float>{}, G);
+    });
 }
 
 void scatter_rows_local(hipStream_t stream,

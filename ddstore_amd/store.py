@@ -66,6 +66,19 @@ class GraphBatch(NamedTuple):
     edge_extras: tuple
 
 
+class RadiusGraphBatch(NamedTuple):
+    """One packed minibatch of graphs whose edges were built from the node
+    positions, as :meth:`DDStore.get_radius_graph_batch` returns it."""
+
+    pos: torch.Tensor          # (Ncap, 3) packed positions, stored dtype
+    edge_index: torch.Tensor   # (2, Ecap), or (Ecap, 2) with coo=False
+    ptr: torch.Tensor          # int64 (n+1,) node offsets
+    edge_ptr: torch.Tensor     # int64 (n+1,) edge offsets
+    batch: torch.Tensor        # int64 (Ncap,) graph id of every node
+    edge_vec: Optional[torch.Tensor]  # float32 (Ecap, 3) pos[src] - pos[dst]
+    node_extras: tuple         # ((values, offsets), ...)
+
+
 class ColumnStats(NamedTuple):
     """Per-column statistics of a variable, as :meth:`DDStore.column_stats`
     returns them. Column ``c`` is flat position ``c`` of a row (CSR: of an
@@ -1180,6 +1193,216 @@ class DDStore:
             ev[edge_end:] = fill
             ev[:edge_end] = kept
         return x, ptr, edge_ptr
+
+    # ----------------------------------------------------------- radius graphs
+    def get_radius_graph_batch(
+        self,
+        pos_name: str,
+        indices: ArrayLike,
+        r: float,
+        *,
+        max_neighbors: Optional[int] = None,
+        loop: bool = False,
+        pos_out: Optional[torch.Tensor] = None,
+        edge_out: Optional[torch.Tensor] = None,
+        batch_out: Optional[torch.Tensor] = None,
+        vec_out: Optional[torch.Tensor] = None,
+        coo: bool = True,
+        edge_dtype: torch.dtype = torch.int64,
+        edge_fill: int = -1,
+        edge_vec: bool = False,
+        node_extras: Sequence[str] = (),
+    ) -> RadiusGraphBatch:
+        """Fetch a minibatch of whole graphs whose edges are a function of the
+        node positions: every pair of nodes of one graph within the cutoff
+        ``r``. Only the positions are stored and moved; the relabelled
+        ``edge_index``, ``edge_ptr``, the ``batch`` vector and, with
+        ``edge_vec=True``, the edge vectors are built natively on the GPU from
+        the packed positions. With the capacity buffers this is one native
+        call with no host sync.
+
+        ``pos_name`` is a plain CSR variable with ``disp == 3``, float32 or
+        float64, ``lengths[i]`` = nodes of graph ``i`` (anything else:
+        ``TypeError``). ``r`` must be positive and finite, ``max_neighbors``
+        ``None`` or an int ``>= 1`` (``ValueError``).
+
+        The rule is exact and the same on both backends. Every coordinate is
+        taken as float32 (float64 rounds to nearest even). For nodes ``i``,
+        ``j`` of one graph ``dx = x_i - x_j`` (likewise ``dy``, ``dz``), ``d2
+        = (dx*dx + dy*dy) + dz*dz`` and ``r2 = f32(r) * f32(r)``, every
+        operation rounded to float32 on its own, no fused multiply-add. There
+        is an edge ``(src=i, dst=j)`` iff ``d2 <= r2`` and (``i != j`` or
+        ``loop``): distinct nodes at one place are neighbours, a NaN
+        coordinate has none. No periodic boundaries.
+
+        A graph's edges are ordered by ``dst``, then ``src``. With
+        ``max_neighbors=K`` every ``dst`` keeps its first ``K`` sources in
+        that order -- the lowest node ids, deterministic, NOT the ``K``
+        nearest.
+
+        With ``n = len(indices)`` the result holds
+
+        * ``pos`` ``(Ncap, 3)`` in the stored dtype: exactly
+          ``get_csr(pos_name, indices, out=pos_out)[0]``; ``ptr`` its offsets;
+        * ``edge_ptr`` int64 ``(n+1,)``: the exclusive scan of the graphs'
+          edge counts after the ``K`` cap. A bad index and a graph whose nodes
+          were not kept (``ptr[i+1] > Ncap``: its positions were never
+          fetched) count 0 edges; otherwise it is not clamped by ``Ecap``;
+        * ``edge_index`` ``(2, Ecap)`` (``(Ecap, 2)`` with ``coo=False``) of
+          ``edge_dtype`` (int64 or int32): edge ``e`` of graph ``i`` at column
+          (row) ``edge_ptr[i] + e``, both ids shifted by ``ptr[i]``;
+        * ``batch`` int64 ``(Ncap,)`` as :meth:`get_graph_batch` gives it;
+        * ``edge_vec`` float32 ``(Ecap, 3)`` or ``None``: row ``edge_ptr[i] +
+          e`` is ``(dx, dy, dz)`` of that edge, ``pos[src] - pos[dst]``.
+
+        Buffers, kept prefixes, the dummy segment ``batch[j] = n``,
+        ``edge_fill``, bad indices, the position variable's counters and
+        ``node_extras`` all follow :meth:`get_graph_batch`: a graph's edges
+        are written iff its nodes were kept and ``edge_ptr[i+1] <= Ecap``,
+        every element of ``batch`` and ``edge_index`` is written, the slack of
+        ``pos`` and the ``edge_vec`` rows of no kept edge stay untouched.
+        ``pos_out``, ``edge_out`` (``2 * Ecap`` ids), ``batch_out`` and, with
+        ``edge_vec=True``, ``vec_out`` (``3 * Ecap`` float32) are passed
+        together or not at all. Without them ``Ncap`` is sized from the host
+        offsets and ``Ecap`` exactly, which takes one read-back of
+        ``edge_ptr[-1]`` between counting and writing the edges: that path
+        syncs with the device, the capacity path does not."""
+        what = "get_radius_graph_batch"
+        self._refuse_mx(what, pos_name)
+        meta = self._meta(pos_name)
+        if (not meta["is_csr"] or meta["disp"] != 3
+                or meta["dtype"] not in (torch.float32, torch.float64)):
+            raise TypeError(
+                f"ddstore {what}: '{pos_name}' must be a CSR variable of float32 "
+                "or float64 with disp == 3")
+        rf = torch.tensor(float(r), dtype=torch.float32)
+        if not (bool(torch.isfinite(rf)) and float(rf) > 0.0):
+            raise ValueError(f"ddstore {what}: r must be positive and finite")
+        if max_neighbors is not None and (
+                int(max_neighbors) != max_neighbors or max_neighbors < 1):
+            raise ValueError(f"ddstore {what}: max_neighbors must be None or an int >= 1")
+        if edge_dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"ddstore {what}: edge_dtype must be int32 or int64")
+        for nm in node_extras:
+            self._graph_extra(nm, pos_name)
+        bufs = (pos_out, edge_out, batch_out) + ((vec_out,) if edge_vec else ())
+        if any(b is None for b in bufs) and not all(b is None for b in bufs):
+            raise ValueError(
+                f"ddstore {what}: pass pos_out, edge_out, batch_out (and vec_out "
+                "with edge_vec=True) together")
+        if not edge_vec and vec_out is not None:
+            raise ValueError(f"ddstore {what}: vec_out needs edge_vec=True")
+        idx = torch.as_tensor(indices, dtype=torch.int64).flatten()
+        fill = int(torch.tensor([edge_fill], dtype=edge_dtype).item())
+        sized = pos_out is None
+        if sized:
+            # Ncap from the host offsets (a device `indices` syncs here); Ecap
+            # after the count
+            ih = idx.cpu()
+            ih = ih[(ih >= 0) & (ih < meta["nrows_total"])]
+            ncap = int((meta["goff"][ih + 1] - meta["goff"][ih]).sum())
+            pos_out = torch.empty((ncap, 3), dtype=meta["dtype"], device=self.device)
+            batch_out = torch.empty(ncap, dtype=torch.int64, device=self.device)
+            edge_out = torch.empty(0, dtype=edge_dtype, device=self.device)
+        else:
+            ncap = pos_out.numel() // 3
+            if (batch_out.dtype != torch.int64 or not batch_out.is_contiguous()
+                    or batch_out.device != self.device or batch_out.numel() != ncap):
+                raise ValueError(
+                    f"ddstore {what}: batch_out must be a contiguous int64 tensor "
+                    f"of {ncap} elements (pos_out's capacity) on the store device")
+            if (edge_out.dtype != edge_dtype or not edge_out.is_contiguous()
+                    or edge_out.device != self.device or edge_out.numel() % 2):
+                raise ValueError(
+                    f"ddstore {what}: edge_out must be a contiguous {edge_dtype} "
+                    "tensor of 2 * Ecap elements on the store device")
+            if edge_vec and (vec_out.dtype != torch.float32 or not vec_out.is_contiguous()
+                             or vec_out.device != self.device
+                             or vec_out.numel() != 3 * (edge_out.numel() // 2)):
+                raise ValueError(
+                    f"ddstore {what}: vec_out must be a contiguous float32 tensor "
+                    "of 3 * Ecap elements on the store device")
+        if vec_out is None:
+            vec_out = torch.empty(0, dtype=torch.float32, device=self.device)
+        if edge_dtype == torch.int32 and ncap >= 2 ** 31:
+            raise ValueError(f"ddstore {what}: int32 node ids need Ncap < 2**31")
+        idx = idx.to(self.device, non_blocking=True).contiguous()
+        k = int(max_neighbors) if max_neighbors is not None else 0
+        self._account(meta, idx)
+        if self.mode == "hip":
+            ptr, edge_ptr, edge_out, vec_out = self._backend.gather_radius_graph(
+                pos_name, idx, float(rf), k, bool(loop), pos_out, edge_out, batch_out,
+                vec_out, bool(edge_vec), sized, bool(coo), fill)
+        else:
+            ptr, edge_ptr, edge_out, vec_out = self._radius_graph_host(
+                pos_name, idx, rf, k, bool(loop), pos_out, edge_out, batch_out,
+                vec_out, bool(edge_vec), sized, bool(coo), fill)
+        ecap = edge_out.numel() // 2
+        return RadiusGraphBatch(
+            pos_out, edge_out.view(2, ecap) if coo else edge_out.view(ecap, 2),
+            ptr, edge_ptr, batch_out.view(ncap),
+            vec_out.view(ecap, 3) if edge_vec else None,
+            tuple(self.get_csr(nm, idx) for nm in node_extras))
+
+    def _radius_graph_host(self, pos_name, idx, rf, k, loop, pos_out, edge_out,
+                           batch_out, vec_out, edge_vec, sized, coo, fill):
+        """Host path of :meth:`get_radius_graph_batch`: the CSR gather, then a
+        brute force per kept graph in float32 torch ops, each of which rounds
+        on its own as the rule asks."""
+        meta = self._meta(pos_name)
+        n, ncap = idx.numel(), pos_out.numel() // 3
+        ok = (idx >= 0) & (idx < meta["nrows_total"])
+        safe = torch.where(ok, idx, torch.zeros_like(idx))
+        goff = meta["goff"]
+        lens = torch.where(ok, goff[safe + 1] - goff[safe], torch.zeros_like(idx))
+        ptr = torch.zeros(n + 1, dtype=torch.int64)
+        torch.cumsum(lens, 0, out=ptr[1:])
+        self._backend.gather_csr(pos_name, idx, ptr, pos_out, ncap)
+        kn = int((ptr[1:] <= ncap).sum())  # ptr is monotone: a prefix is kept
+        node_end = int(ptr[kn])
+        batch = batch_out.view(ncap)
+        batch[node_end:] = n
+        batch[:node_end] = torch.repeat_interleave(
+            torch.arange(kn, dtype=torch.int64), lens[:kn])
+        r2 = rf * rf
+        p32 = pos_out.view(ncap, 3)[:node_end].to(torch.float32)
+        pairs, vecs = [], []
+        edge_ptr = torch.zeros(n + 1, dtype=torch.int64)
+        for s in range(kn):
+            p = p32[int(ptr[s]):int(ptr[s + 1])]
+            d = p[:, None, :] - p[None, :, :]         # d[i, j] = pos[i] - pos[j]
+            d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            m = (d2 <= r2).t()                        # m[dst, src]
+            if not loop:
+                m.fill_diagonal_(False)
+            if k:
+                m &= torch.cumsum(m, 1) <= k          # the first k sources per dst
+            dst, src = m.nonzero(as_tuple=True)       # by dst, then src
+            edge_ptr[s + 1] = dst.numel()
+            pairs.append(torch.stack([src, dst], 1) + ptr[s])
+            vecs.append(d[src, dst])
+        torch.cumsum(edge_ptr[1:].clone(), 0, out=edge_ptr[1:])
+        if sized:
+            total = int(edge_ptr[-1])
+            edge_out = torch.empty(2 * total, dtype=edge_out.dtype)
+            if edge_vec:
+                vec_out = torch.empty(3 * total, dtype=torch.float32)
+        ecap = edge_out.numel() // 2
+        ke = min(kn, int((edge_ptr[1:] <= ecap).sum()))
+        edge_end = int(edge_ptr[ke])
+        kept = (torch.cat(pairs[:ke]) if ke else torch.zeros((0, 2), dtype=torch.int64))
+        kept = kept.to(edge_out.dtype)
+        if coo:
+            ev = edge_out.view(2, ecap)
+            ev[:, edge_end:] = fill
+            ev[:, :edge_end] = kept.t()
+        else:
+            ev = edge_out.view(ecap, 2)
+            ev[edge_end:] = fill
+            ev[:edge_end] = kept
+        if edge_vec and ke:
+            vec_out.view(ecap, 3)[:edge_end] = torch.cat(vecs[:ke])
+        return ptr, edge_ptr, edge_out, vec_out
 
     def local_shard(self, name: str) -> torch.Tensor:
         """Zero-copy view of this rank's shard (rows x disp). Valid until
