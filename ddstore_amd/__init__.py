@@ -7,7 +7,8 @@ RCCL (torch.distributed "nccl") metadata plane, POSIX-shm CPU compatibility
 path. See ddstore_amd/csrc for the native core.
 """
 from .comm import Comm, as_comm
-from .store import ColumnStats, DDStore, GraphBatch, RadiusGraphBatch
+from .store import (ColumnStats, DDStore, GraphBatch, PeriodicGraphBatch,
+                    RadiusGraphBatch)
 from .distdataset import DistDataset, nsplit
 from .prefetch import GraphPrefetchLoader, PrefetchLoader
 from .reshuffle import reshuffle_epoch
@@ -21,6 +22,7 @@ __all__ = [
     "DDStore",
     "GraphBatch",
     "RadiusGraphBatch",
+    "PeriodicGraphBatch",
     "ColumnStats",
     "DistDataset",
     "nsplit",

@@ -1047,6 +1047,122 @@ public:
         return {ptr, edge_ptr, edge_out, vec_out};
     }
 
+    // Periodic radius-graph fetch in one native call: gather_radius_graph with
+    // the translated images of every node. The cell variable (fixed stride, 9
+    // columns of f32 or f64, one row per graph) is fetched for the same
+    // indices by the fixed-stride gather into an (n, 3, 3) tensor of its
+    // stored dtype, then radius_pbc_count / radius_pbc_fill build the edges
+    // by the rule in ddstore_kernels.h. pbc has bit k set for a periodic axis.
+    // shift_out holds 3 * Ecap int32 and is sized here with the other edge
+    // buffers under size_edges. Returns (ptr, edge_ptr, edge_out, shift_out,
+    // vec_out, cell, shifts_needed); shifts_needed is int32 (n, 3). shift_out
+    // and vec_out are written only on rows of kept edges, a bad index leaves
+    // its cell row untouched.
+    std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+               at::Tensor>
+    gather_radius_graph_pbc(const std::string& pos_name, const std::string& cell_name,
+                            const at::Tensor& idx, double r, int64_t pbc,
+                            int64_t max_shift, bool loop, at::Tensor pos_out,
+                            at::Tensor edge_out, at::Tensor batch_out,
+                            at::Tensor shift_out, at::Tensor vec_out, bool edge_vec,
+                            bool size_edges, bool coo, int64_t edge_fill) {
+        RoctxRange rr_("ddstore::gather_radius_graph_pbc");
+        const char* op = "ddstore gather_radius_graph_pbc: ";
+        DeviceVar& pv = var(pos_name);
+        DeviceVar& cv = var(cell_name);
+        TORCH_CHECK(pv.is_csr, op, "not a CSR variable");
+        check_peers(pv);
+        check_idx(idx);
+        TORCH_CHECK(pv.mx_elem < 0 && pv.row_elems == 3 &&
+                        (pv.dds_t == DDS_F32 || pv.dds_t == DDS_F64),
+                    op, "positions must be a plain f32/f64 CSR variable with disp == 3");
+        TORCH_CHECK(!cv.is_csr && cv.mx_elem < 0 && cv.row_elems == 9 &&
+                        (cv.dds_t == DDS_F32 || cv.dds_t == DDS_F64),
+                    op, "cells must be a plain f32/f64 fixed-stride variable with "
+                        "disp == 9");
+        TORCH_CHECK(cv.nrows_total() == pv.nrows_total(), op,
+                    "the cell variable must have one row per graph");
+        const float rf = (float)r;
+        TORCH_CHECK(std::isfinite(rf) && rf > 0.0f, op, "r must be positive and finite");
+        TORCH_CHECK(max_shift >= 1 && max_shift <= 8, op, "max_shift must be in 1..8");
+        TORCH_CHECK(pbc >= 0 && pbc < 8, op, "pbc is a mask of three axes");
+        const int64_t nidx = idx.numel();
+        const int64_t ncap = pos_out.numel() / 3;
+        TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
+                        batch_out.device().is_cuda() &&
+                        batch_out.device().index() == device_ &&
+                        batch_out.numel() == ncap,
+                    op, "batch_out must be a contiguous int64 tensor of pos_out's "
+                        "capacity on the store device");
+        TORCH_CHECK(edge_out.scalar_type() == at::kLong ||
+                        edge_out.scalar_type() == at::kInt,
+                    op, "edge ids are int64 or int32");
+        const int out_t = dds_type_of(edge_out);
+        TORCH_CHECK(out_t == DDS_I64 || ncap < (int64_t(1) << 31),
+                    op, "int32 node ids need Ncap < 2^31");
+        at::Tensor ptr = csr_fast(pv, idx, pos_out);
+        auto opts = at::TensorOptions().dtype(at::kLong).device(idx.device());
+        at::Tensor cell = at::empty(
+            {nidx, 3, 3}, opts.dtype(cv.dds_t == DDS_F64 ? at::kDouble : at::kFloat));
+        gather_fixed(cell_name, idx, cell, Affine{});
+        at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
+        at::Tensor needed = at::empty({nidx, 3}, opts.dtype(at::kInt));
+        at::Tensor scratch = at::empty(
+            {(int64_t)ddstore::radius_pbc_scratch_bytes(nidx)}, opts.dtype(at::kByte));
+        if (nidx == 0) {
+            edge_ptr.zero_();
+        } else {
+            ddstore::radius_pbc_count(
+                stream(), pos_out.data_ptr(), pv.dds_t, cell.data_ptr(), cv.dds_t,
+                ptr.data_ptr<int64_t>(), idx.data_ptr<int64_t>(), nidx, pv.nrows_total(),
+                ncap, rf, (int)pbc, (int)max_shift, loop, scratch.data_ptr(),
+                edge_ptr.data_ptr<int64_t>(), needed.data_ptr<int32_t>());
+        }
+        if (size_edges) {
+            const int64_t total = nidx ? edge_ptr[nidx].item<int64_t>() : 0;  // syncs
+            edge_out = at::empty({2 * total}, edge_out.options());
+            shift_out = at::empty({total, 3}, edge_out.options().dtype(at::kInt));
+            if (edge_vec)
+                vec_out = at::empty({total, 3}, edge_out.options().dtype(at::kFloat));
+        }
+        TORCH_CHECK(edge_out.is_contiguous() && edge_out.device().is_cuda() &&
+                        edge_out.device().index() == device_ &&
+                        edge_out.numel() % 2 == 0,
+                    op, "edge_out must be a contiguous tensor of 2 * Ecap ids on the "
+                        "store device");
+        const int64_t ecap = edge_out.numel() / 2;
+        TORCH_CHECK((uintptr_t)edge_out.data_ptr() % dds_itemsize(out_t) == 0 &&
+                        (uintptr_t)batch_out.data_ptr() % 8 == 0,
+                    op, "misaligned output");
+        TORCH_CHECK(shift_out.scalar_type() == at::kInt && shift_out.is_contiguous() &&
+                        shift_out.device().is_cuda() &&
+                        shift_out.device().index() == device_ &&
+                        shift_out.numel() == 3 * ecap,
+                    op, "shift_out must be a contiguous int32 tensor of 3 * Ecap "
+                        "elements on the store device");
+        float* d_vec = nullptr;
+        if (edge_vec) {
+            TORCH_CHECK(vec_out.scalar_type() == at::kFloat && vec_out.is_contiguous() &&
+                            vec_out.device().is_cuda() &&
+                            vec_out.device().index() == device_ &&
+                            vec_out.numel() == 3 * ecap,
+                        op, "vec_out must be a contiguous float32 tensor of 3 * Ecap "
+                            "elements on the store device");
+            d_vec = ecap ? vec_out.data_ptr<float>() : nullptr;
+        }
+        if (nidx > 0 && ecap > 0)
+            ddstore::radius_pbc_fill(
+                stream(), pos_out.data_ptr(), pv.dds_t, ptr.data_ptr<int64_t>(),
+                edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, rf, (int)pbc, loop,
+                scratch.data_ptr(), out_t, coo, edge_out.data_ptr(),
+                shift_out.data_ptr<int32_t>(), d_vec);
+        ddstore::graph_fill(stream(), ptr.data_ptr<int64_t>(),
+                            edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, out_t, coo,
+                            edge_fill, batch_out.data_ptr<int64_t>(),
+                            edge_out.data_ptr());
+        return {ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed};
+    }
+
     // Padded CSR fetch: one launch writes the dense (n, max_len, disp)
     // batch (cast / affine fused, pad broadcast from `pad_bits`, the raw
     // bits of one output element) and the true per-sample lengths. The

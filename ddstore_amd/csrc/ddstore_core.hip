@@ -83,6 +83,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("gather_graph", &DeviceStore::gather_graph, py::call_guard<py::gil_scoped_release>())
         .def("gather_radius_graph", &DeviceStore::gather_radius_graph,
              py::call_guard<py::gil_scoped_release>())
+        .def("gather_radius_graph_pbc", &DeviceStore::gather_radius_graph_pbc,
+             py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_padded", &DeviceStore::gather_csr_padded,
              py::arg("name"), py::arg("idx"), py::arg("out"), py::arg("lengths"),
              py::arg("max_len"), py::arg("pad_bits"), py::arg("affine") = false,

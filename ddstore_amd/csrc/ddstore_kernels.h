@@ -277,6 +277,43 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
                  const void* d_scratch, int out_t, bool coo, void* d_edge_out,
                  float* d_vec_out);
 
+// Periodic radius-graph fetch (DeviceStore::gather_radius_graph_pbc): as
+// above, with the translated images of every node. d_cell is the (nidx, 9)
+// array of cell_t (DDS_F32 or DDS_F64) the fixed-stride gather has just
+// written for the same indices d_idx, row s the cell of request s (lattice
+// vector a_k at 3k..3k+2); nsamples is the variable's global sample count, so
+// a bad index, whose cell row was not written, is never read. pbc has bit k
+// set for a periodic axis k; max_shift is in 1..8.
+//
+// Rule (docs/API.md): per graph needed_k = floor(q * (1 + 2^-10)) + 1 with q
+// = r * |a_i x a_j| / |det| in f32, INT32_MAX for a zero-volume or non-finite
+// cell, 0 on a non-periodic axis; b_k = min(max_shift, needed_k); the images
+// are the triples s with |s_k| <= b_k. dx = (x_i - x_j) + t_x with t = (s0*a0
+// + s1*a1) + s2*a2, nothing added for s = 0; d2 and r2 as above. (src = i,
+// dst = j, s) is an edge iff d2 <= r2 and (i != j or s != 0 or loop). A
+// graph's edges are ordered by dst, then s (lexicographic, ascending), then
+// src.
+//
+// radius_pbc_count: d_edge_ptr as radius_count leaves it, and d_needed[3s..]
+// = needed of request s, unclamped, 0 for a bad index and for a graph whose
+// nodes were not kept. d_scratch: radius_pbc_scratch_bytes(nidx) bytes, no
+// zeroing needed. Two launches.
+//
+// radius_pbc_fill: as radius_fill, and row d_edge_ptr[s] + e of the (ecap, 3)
+// int32 array d_shift_out is the edge's s. One launch; no atomics and no
+// counters in either.
+size_t radius_pbc_scratch_bytes(int64_t nidx);
+void radius_pbc_count(hipStream_t stream, const void* d_pos, int pos_t,
+                      const void* d_cell, int cell_t, const int64_t* d_ptr,
+                      const int64_t* d_idx, int64_t nidx, int64_t nsamples,
+                      int64_t ncap, float r, int pbc, int max_shift, bool loop,
+                      void* d_scratch, int64_t* d_edge_ptr, int32_t* d_needed);
+void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                     const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                     int64_t ncap, int64_t ecap, float r, int pbc, bool loop,
+                     const void* d_scratch, int out_t, bool coo, void* d_edge_out,
+                     int32_t* d_shift_out, float* d_vec_out);
+
 // MX (OCP microscaling v1.0) block-scaled storage. A variable of logical
 // width `disp` keeps each row packed as
 //   [nblk * 32 element codes][nblk E8M0 scale bytes][zero pad to 16 B]

@@ -1628,6 +1628,345 @@ k_radius_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
 }
 
 // ---------------------------------------------------------------------------
+// Periodic radius-graph fetch: the edges of a batch of periodic structures,
+// image shifts included, from the packed positions and the (n, 9) cells the
+// fixed-stride gather has just written. Two kernels between those gathers and
+// k_graph_fill, with k_radius_scan between them:
+//   k_radius_pbc_count  per-graph image box, shifts_needed and edge count
+//   k_radius_pbc_fill   the kept graphs' edges, shifts and edge vectors
+// The rule (docs/API.md, "Radius graphs"): dx = (x_src - x_dst) + t_x with
+// t = (s0*a0 + s1*a1) + s2*a2 per component, nothing added for s = 0, every
+// operation rounded to f32 on its own; edge iff d2 <= r2 and (src != dst or
+// s != 0 or loop).
+//
+// Mapping, both passes: GROUP lanes per graph on the persistent grid of the
+// non-periodic kernels, the graph's positions in the group's LDS slice
+// (radius_stage, tiles streamed for larger graphs). The unit of work is an
+// item (dst j, image m), numbered j * nimg + m, and the items of a graph are
+// flattened across the lanes: block `ib` of kPbcItems * GROUP items gives lane
+// `tid` the items ib + c * GROUP + tid. A 4-atom cell with 125 images and a
+// 200-atom cell with 27 both fill a wave; one centre per lane would leave 60
+// lanes idle on the first. A lane decodes m to s, forms t from the cell (kept
+// in registers, group-uniform) and holds (x_j, y_j, z_j, t) of its items; all
+// lanes walk the sources in step, so every LDS read is a broadcast that serves
+// kPbcItems images. The number of items in use is the same in every lane of a
+// group but the last round, which the walk is specialised on.
+//
+// The count pass computes the box: needed_k = floor(q * (1 + 2^-10)) + 1 with
+// q = r * |a_i x a_j| / |det| in f32 (INT32_MAX for a zero-volume or
+// non-finite cell), b_k = min(max_shift, needed_k) on periodic axes. It
+// leaves the f32 cell and b in a 48-byte record per graph for the fill pass;
+// there is no per-node or per-item scratch.
+//
+// Edge order is item order (dst, then shift, then src), so the fill pass needs
+// every item's count before it can place the item's run. It counts a block of
+// items in registers, scans the counts across the group (a carry joins the
+// blocks), and walks the sources a second time to write: three walks per fetch
+// and no atomics. Staging a block's edges in LDS to flush them coalesced was
+// not tried, and neither was a per-image cull (most images of a cell larger
+// than 2r hold no edge).
+//
+// GROUP is 16 when the request's items per graph, estimated on the host as
+// mean nodes * 3^(periodic axes), stay under 96 and 64 otherwise
+// (DDSTORE_RADIUS_PBC_GROUP overrides it for A/B runs).
+//
+// Measured on MI355X (profiles/radius_pbc_ab.txt), 8,192 structures of 2..64
+// atoms, f32, orthorhombic and triclinic cells at 4.5 atoms per unit volume,
+// r = 1.0 (one or two layers per axis), 269 k atoms, 4.92 M edges, 311 M (pair
+// x image) tests per walk, int64 ids, exact capacities: the whole fetch
+// 1.01 ms (1.05 ms with edge vectors) against 91.3 ms for get_csr and
+// get_batch plus a torch construction of the image box. Per kernel: count
+// 228 us, scan 10 us, fill 736 us (two walks and 4.9 M scattered edges),
+// k_graph_fill 15 us; 3.2 ps per test against 11.1 ps per pair of the
+// non-periodic call on the same positions. GROUP = 16 forced at this shape:
+// 1.60 ms. kPbcItems and the grids were chosen by construction and not swept.
+// ---------------------------------------------------------------------------
+
+constexpr int kPbcItems = 4;  // items a lane keeps in registers
+
+// What the count pass leaves per graph for the fill pass.
+struct PbcBox {
+    float a[9];  // the cell by the cast rule, lattice vector k at 3k..3k+2
+    int b[3];    // image layers searched per axis
+};
+static_assert(sizeof(PbcBox) == 48, "radius_pbc_scratch_bytes counts 48 bytes");
+
+// Layers needed along the axis whose two other lattice vectors have the cross
+// product (cx, cy, cz); adet = |det(cell)|.
+__device__ __forceinline__ int pbc_needed(float rf, float cx, float cy, float cz,
+                                          float adet) {
+#pragma clang fp contract(off)
+    const float nrm = sqrtf((cx * cx + cy * cy) + cz * cz);
+    const float q = (rf * nrm) / adet;
+    const float f = floorf(q * 1.0009765625f);
+    return (adet > 0.0f && adet < __builtin_inff() && f < 1073741824.0f)
+               ? (int)f + 1 : INT32_MAX;
+}
+
+// needed[0..3) of a cell; 0 on non-periodic axes.
+__device__ __forceinline__ void pbc_layers(const float (&a)[9], float rf, int pbc,
+                                           int (&needed)[3]) {
+#pragma clang fp contract(off)
+    float c[9];  // c[3k..] = a_(k+1) x a_(k+2)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float* u = a + 3 * ((k + 1) % 3);
+        const float* v = a + 3 * ((k + 2) % 3);
+        c[3 * k] = u[1] * v[2] - u[2] * v[1];
+        c[3 * k + 1] = u[2] * v[0] - u[0] * v[2];
+        c[3 * k + 2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const float det = (a[0] * c[0] + a[1] * c[1]) + a[2] * c[2];
+    const float adet = fabsf(det);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        needed[k] = (pbc >> k & 1)
+                        ? pbc_needed(rf, c[3 * k], c[3 * k + 1], c[3 * k + 2], adet) : 0;
+}
+
+// The items of one round of a lane: item c is number ib + c * GROUP + tid of
+// the graph. Past the end (q >= nitems) the dst position is NaN, which is
+// nobody's neighbour.
+template <typename Tin, int GROUP>
+struct PbcItems {
+    float x[kPbcItems], y[kPbcItems], z[kPbcItems];
+    float tx[kPbcItems], ty[kPbcItems], tz[kPbcItems];
+    int64_t j[kPbcItems];
+    int s[kPbcItems][3];
+    bool zero[kPbcItems];  // the image (0, 0, 0): nothing is added
+
+    __device__ __forceinline__ void load(const Tin* __restrict__ gp, const PbcBox& box,
+                                         int nimg, int64_t nitems, int64_t ib, int tid) {
+#pragma clang fp contract(off)
+        const int n1 = 2 * box.b[1] + 1, n2 = 2 * box.b[2] + 1;
+#pragma unroll
+        for (int c = 0; c < kPbcItems; ++c) {
+            const int64_t q = ib + c * GROUP + tid;
+            const bool in = q < nitems;
+            int m;
+            if (nitems <= INT32_MAX) {  // group-uniform: the 32-bit division
+                j[c] = (uint32_t)q / (uint32_t)nimg;
+                m = (int)((uint32_t)q - (uint32_t)j[c] * (uint32_t)nimg);
+            } else {
+                j[c] = q / nimg;
+                m = (int)(q - j[c] * nimg);
+            }
+            const int m01 = m / n2;
+            s[c][2] = m - m01 * n2 - box.b[2];
+            s[c][0] = m01 / n1;
+            s[c][1] = m01 - s[c][0] * n1 - box.b[1];
+            s[c][0] -= box.b[0];
+            zero[c] = (s[c][0] | s[c][1] | s[c][2]) == 0;
+            const float f0 = (float)s[c][0], f1 = (float)s[c][1], f2 = (float)s[c][2];
+            tx[c] = (f0 * box.a[0] + f1 * box.a[3]) + f2 * box.a[6];
+            ty[c] = (f0 * box.a[1] + f1 * box.a[4]) + f2 * box.a[7];
+            tz[c] = (f0 * box.a[2] + f1 * box.a[5]) + f2 * box.a[8];
+            x[c] = in ? radius_coord(gp[3 * j[c]]) : __builtin_nanf("");
+            y[c] = in ? radius_coord(gp[3 * j[c] + 1]) : 0.0f;
+            z[c] = in ? radius_coord(gp[3 * j[c] + 2]) : 0.0f;
+        }
+    }
+};
+
+// Sources [0, tn) of the slice against the first R items of the lane;
+// hit(c, i, dx, dy, dz) for every edge, sources ascending. self[c] is the
+// slot an item must skip (its own dst under the zero image without loop), or
+// -1.
+template <int R, typename I, typename Hit>
+__device__ __forceinline__ void pbc_walk(const float* sl, int tn, const I& it,
+                                         const int (&self)[kPbcItems], float r2,
+                                         Hit&& hit) {
+#pragma clang fp contract(off)
+    for (int i = 0; i < tn; ++i) {
+        const float sx = sl[i], sy = sl[kRadiusTile + i], sz = sl[2 * kRadiusTile + i];
+#pragma unroll
+        for (int c = 0; c < R; ++c) {
+            float dx = sx - it.x[c], dy = sy - it.y[c], dz = sz - it.z[c];
+            if (!it.zero[c]) {
+                dx = dx + it.tx[c];
+                dy = dy + it.ty[c];
+                dz = dz + it.tz[c];
+            }
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 <= r2 && i != self[c]) hit(c, i, dx, dy, dz);
+        }
+    }
+}
+
+// All sources of graph `gp` (n nodes) against the items of one round, tile by
+// tile; a graph of one tile was staged by the caller (`staged`).
+// hit(c, src, dx, dy, dz) with src the node's index in the graph.
+template <typename Tin, int GROUP, typename Hit>
+__device__ __forceinline__ void pbc_pass(float* sl, const Tin* __restrict__ gp,
+                                         int64_t n, bool staged,
+                                         const PbcItems<Tin, GROUP>& it, int64_t ib,
+                                         int64_t nitems, int tid, float r2, bool loop,
+                                         Hit&& hit) {
+    // items in use: the same number in every lane of the group
+    const int64_t left = (nitems - ib + GROUP - 1) / GROUP;
+    const int nr = left < kPbcItems ? (int)left : kPbcItems;
+    for (int64_t t0 = 0; t0 < n; t0 += kRadiusTile) {
+        const int tn = n - t0 < kRadiusTile ? (int)(n - t0) : kRadiusTile;
+        if (!staged) {
+            group_lds_sync();  // the walk of the tile before is done
+            radius_stage<Tin, GROUP>(sl, gp + 3 * t0, tn, tid);
+            group_lds_sync();
+        }
+        int self[kPbcItems];
+#pragma unroll
+        for (int c = 0; c < kPbcItems; ++c) {
+            const int64_t d = it.j[c] - t0;
+            self[c] = !loop && it.zero[c] && d >= 0 && d < tn ? (int)d : -1;
+        }
+        auto at = [&](int c, int i, float dx, float dy, float dz) {
+            hit(c, t0 + i, dx, dy, dz);
+        };
+        switch (nr) {
+            case 1: pbc_walk<1>(sl, tn, it, self, r2, at); break;
+            case 2: pbc_walk<2>(sl, tn, it, self, r2, at); break;
+            case 3: pbc_walk<3>(sl, tn, it, self, r2, at); break;
+            default: pbc_walk<4>(sl, tn, it, self, r2, at); break;
+        }
+    }
+}
+static_assert(kPbcItems == 4, "pbc_pass dispatches 1..4 items");
+
+// Box, shifts_needed and per-graph counts. For every request s: needed[3s..]
+// (0 for a bad index and for a graph whose nodes were not kept) and counts[s]
+// (0 for those and for an empty graph); box[s] for every kept graph.
+template <typename Tin, typename Tcell, int GROUP>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_radius_pbc_count(const Tin* __restrict__ pos, const Tcell* __restrict__ cell,
+                   const int64_t* __restrict__ ptr, const int64_t* __restrict__ idx,
+                   int64_t nidx, int64_t nsamples, int64_t ncap, float rf, float r2,
+                   int pbc, int max_shift, bool loop, int64_t* __restrict__ counts,
+                   PbcBox* __restrict__ boxes, int32_t* __restrict__ needed_out) {
+    constexpr int GPB = kBlock / GROUP;
+    __shared__ float s_pos[GPB * kRadiusSlice];
+    float* sl = s_pos + (threadIdx.x / GROUP) * kRadiusSlice;
+    const int tid = threadIdx.x % GROUP;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        const int64_t n = p1 - p0;
+        const int64_t g = idx[s];
+        const bool kept = g >= 0 && g < nsamples && p0 >= 0 && p1 <= ncap;
+        int64_t total = 0;
+        int needed[3] = {0, 0, 0};
+        if (kept) {
+            PbcBox box;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) box.a[k] = radius_coord(cell[9 * s + k]);
+            pbc_layers(box.a, rf, pbc, needed);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                box.b[k] = needed[k] < max_shift ? needed[k] : max_shift;
+            if (tid == 0) boxes[s] = box;
+            const int nimg = (2 * box.b[0] + 1) * (2 * box.b[1] + 1) * (2 * box.b[2] + 1);
+            const int64_t nitems = n * nimg;
+            const Tin* __restrict__ gp = pos + 3 * p0;
+            const bool staged = n <= kRadiusTile;
+            if (staged && n > 0) {
+                group_lds_sync();  // the graph before is done with the slice
+                radius_stage<Tin, GROUP>(sl, gp, (int)n, tid);
+                group_lds_sync();
+            }
+            for (int64_t ib = 0; ib < nitems; ib += kPbcItems * GROUP) {
+                PbcItems<Tin, GROUP> it;
+                it.load(gp, box, nimg, nitems, ib, tid);
+                int cnt = 0;
+                pbc_pass<Tin, GROUP>(sl, gp, n, staged, it, ib, nitems, tid, r2, loop,
+                                     [&](int, int64_t, float, float, float) { ++cnt; });
+                total += cnt;
+            }
+        }
+        for (int off = GROUP / 2; off > 0; off >>= 1) total += __shfl_xor(total, off, GROUP);
+        if (tid == 0) {
+            counts[s] = total;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) needed_out[3 * s + k] = needed[k];
+        }
+    }
+}
+
+// The edges of every graph with ptr[s+1] <= ncap and edge_ptr[s+1] <= ecap:
+// edge e of the graph (item order, then src ascending) at column edge_ptr[s] +
+// e of a (2, ecap) output (coo) or at that row of an (ecap, 2) one, both ids
+// shifted by ptr[s]; row edge_ptr[s] + e of shift is its image s and, with
+// VEC, that row of vec (dx, dy, dz). Nothing else is written.
+template <typename Tin, typename Tout, int GROUP, bool VEC>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_radius_pbc_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
+                  const int64_t* __restrict__ edge_ptr, int64_t nidx, int64_t ncap,
+                  int64_t ecap, float r2, bool loop, const PbcBox* __restrict__ boxes,
+                  bool coo, Tout* __restrict__ out, int32_t* __restrict__ shift,
+                  float* __restrict__ vec) {
+    constexpr int GPB = kBlock / GROUP;
+    __shared__ float s_pos[GPB * kRadiusSlice];
+    float* sl = s_pos + (threadIdx.x / GROUP) * kRadiusSlice;
+    const int tid = threadIdx.x % GROUP;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        const int64_t e0 = edge_ptr[s], e1 = edge_ptr[s + 1];
+        const int64_t n = p1 - p0;
+        // a graph with edges was kept by the count pass: its box is there
+        if (n <= 0 || p0 < 0 || p1 > ncap || e1 <= e0 || e0 < 0 || e1 > ecap) continue;
+        const PbcBox box = boxes[s];
+        const int nimg = (2 * box.b[0] + 1) * (2 * box.b[1] + 1) * (2 * box.b[2] + 1);
+        const int64_t nitems = n * nimg;
+        const Tin* __restrict__ gp = pos + 3 * p0;
+        const bool staged = n <= kRadiusTile;
+        if (staged) {
+            group_lds_sync();
+            radius_stage<Tin, GROUP>(sl, gp, (int)n, tid);
+            group_lds_sync();
+        }
+        int64_t carry = e0;  // first edge slot of the next item
+        for (int64_t ib = 0; ib < nitems; ib += kPbcItems * GROUP) {
+            PbcItems<Tin, GROUP> it;
+            it.load(gp, box, nimg, nitems, ib, tid);
+            int d[kPbcItems] = {0, 0, 0, 0};
+            pbc_pass<Tin, GROUP>(sl, gp, n, staged, it, ib, nitems, tid, r2, loop,
+                                 [&](int c, int64_t, float, float, float) { ++d[c]; });
+            int64_t at[kPbcItems];  // next edge slot of each item
+#pragma unroll
+            for (int c = 0; c < kPbcItems; ++c) {
+                int incl = d[c];
+                for (int off = 1; off < GROUP; off <<= 1) {
+                    const int a = __shfl_up(incl, off, GROUP);
+                    if (tid >= off) incl += a;
+                }
+                at[c] = carry + (incl - d[c]);
+                carry += __shfl(incl, GROUP - 1, GROUP);
+            }
+            if (carry > e1) break;  // never: both passes count by one rule
+            pbc_pass<Tin, GROUP>(
+                sl, gp, n, staged, it, ib, nitems, tid, r2, loop,
+                [&](int c, int64_t src, float dx, float dy, float dz) {
+                    const int64_t o = at[c]++;
+                    const Tout a = static_cast<Tout>(src + p0);
+                    const Tout b = static_cast<Tout>(it.j[c] + p0);
+                    if (coo) {
+                        out[o] = a;
+                        out[ecap + o] = b;
+                    } else {
+                        reinterpret_cast<IdPair<Tout>*>(out)[o] = IdPair<Tout>{a, b};
+                    }
+                    shift[3 * o] = it.s[c][0];
+                    shift[3 * o + 1] = it.s[c][1];
+                    shift[3 * o + 2] = it.s[c][2];
+                    if constexpr (VEC) {
+                        vec[3 * o] = dx;
+                        vec[3 * o + 1] = dy;
+                        vec[3 * o + 2] = dz;
+                    }
+                });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Local scatter (reshuffle placement): row r of src -> local row
 // local_idx[r] of base. Same chunk mapping as gather.
 // ---------------------------------------------------------------------------
@@ -2532,6 +2871,91 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
     auto launch_out = [&](auto ti, auto G) {
         if (out_t == DDS_I64) launch_flags(ti, TypeTag<int64_t>{}, G);
         else if (out_t == DDS_I32) launch_flags(ti, TypeTag<int32_t>{}, G);
+    };
+    dispatch_group<16, 64>(group, [&](auto G) {
+        if (pos_t == DDS_F64) launch_out(TypeTag<double>{}, G);
+        else if (pos_t == DDS_F32) launch_out(TypeTag<float>{}, G);
+    });
+}
+
+size_t radius_pbc_scratch_bytes(int64_t nidx) {
+    return (size_t)(nidx + 1) * (8 + sizeof(PbcBox));
+}
+
+namespace {
+
+// Lanes per graph of the periodic kernels (see the section note); the
+// environment override is for A/B runs.
+int radius_pbc_group(int64_t nidx, int64_t ncap, int pbc) {
+    static const int forced = [] {
+        const char* e = getenv("DDSTORE_RADIUS_PBC_GROUP");
+        const int v = e ? atoi(e) : 0;
+        return (v == 16 || v == 64) ? v : 0;
+    }();
+    if (forced) return forced;
+    int64_t items = ncap / (nidx > 0 ? nidx : 1);  // with one layer per periodic axis
+    for (int k = 0; k < 3; ++k)
+        if (pbc >> k & 1) items *= 3;
+    return items < 96 ? 16 : 64;
+}
+
+}  // namespace
+
+void radius_pbc_count(hipStream_t stream, const void* d_pos, int pos_t,
+                      const void* d_cell, int cell_t, const int64_t* d_ptr,
+                      const int64_t* d_idx, int64_t nidx, int64_t nsamples,
+                      int64_t ncap, float r, int pbc, int max_shift, bool loop,
+                      void* d_scratch, int64_t* d_edge_ptr, int32_t* d_needed) {
+    if (nidx == 0) return;
+    int64_t* counts = reinterpret_cast<int64_t*>(d_scratch);
+    PbcBox* boxes = reinterpret_cast<PbcBox*>(counts + nidx + 1);
+    const int group = radius_pbc_group(nidx, ncap, pbc);
+    const int grid = radius_grid(nidx, group);
+    auto launch = [&](auto ti, auto tc, auto G) {
+        using Tin = typename decltype(ti)::type;
+        using Tcell = typename decltype(tc)::type;
+        hipLaunchKernelGGL((k_radius_pbc_count<Tin, Tcell, G()>), dim3(grid),
+                           dim3(kBlock), 0, stream, (const Tin*)d_pos,
+                           (const Tcell*)d_cell, d_ptr, d_idx, nidx, nsamples, ncap, r,
+                           r * r, pbc, max_shift, loop, counts, boxes, d_needed);
+    };
+    auto launch_cell = [&](auto ti, auto G) {
+        if (cell_t == DDS_F64) launch(ti, TypeTag<double>{}, G);
+        else if (cell_t == DDS_F32) launch(ti, TypeTag<float>{}, G);
+    };
+    dispatch_group<16, 64>(group, [&](auto G) {
+        if (pos_t == DDS_F64) launch_cell(TypeTag<double>{}, G);
+        else if (pos_t == DDS_F32) launch_cell(TypeTag<float>{}, G);
+    });
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, counts, nidx,
+                       d_edge_ptr);
+}
+
+void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                     const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                     int64_t ncap, int64_t ecap, float r, int pbc, bool loop,
+                     const void* d_scratch, int out_t, bool coo, void* d_edge_out,
+                     int32_t* d_shift_out, float* d_vec_out) {
+    if (nidx == 0 || ecap == 0) return;
+    const PbcBox* boxes = reinterpret_cast<const PbcBox*>(
+        reinterpret_cast<const int64_t*>(d_scratch) + nidx + 1);
+    const int group = radius_pbc_group(nidx, ncap, pbc);
+    const int grid = radius_grid(nidx, group);
+    auto launch = [&](auto ti, auto to, auto G, auto v) {
+        using Tin = typename decltype(ti)::type;
+        using Tout = typename decltype(to)::type;
+        hipLaunchKernelGGL((k_radius_pbc_fill<Tin, Tout, G(), decltype(v)::value>),
+                           dim3(grid), dim3(kBlock), 0, stream, (const Tin*)d_pos, d_ptr,
+                           d_edge_ptr, nidx, ncap, ecap, r * r, loop, boxes, coo,
+                           (Tout*)d_edge_out, d_shift_out, d_vec_out);
+    };
+    auto launch_out = [&](auto ti, auto G) {
+        auto with_vec = [&](auto to) {
+            if (d_vec_out) launch(ti, to, G, std::true_type{});
+            else launch(ti, to, G, std::false_type{});
+        };
+        if (out_t == DDS_I64) with_vec(TypeTag<int64_t>{});
+        else if (out_t == DDS_I32) with_vec(TypeTag<int32_t>{});
     };
     dispatch_group<16, 64>(group, [&](auto G) {
         if (pos_t == DDS_F64) launch_out(TypeTag<double>{}, G);

@@ -79,6 +79,23 @@ class RadiusGraphBatch(NamedTuple):
     node_extras: tuple         # ((values, offsets), ...)
 
 
+class PeriodicGraphBatch(NamedTuple):
+    """One packed minibatch of periodic structures whose edges, image shifts
+    included, were built from positions and cells, as
+    :meth:`DDStore.get_radius_graph_pbc_batch` returns it."""
+
+    pos: torch.Tensor          # (Ncap, 3) packed positions, stored dtype
+    edge_index: torch.Tensor   # (2, Ecap), or (Ecap, 2) with coo=False
+    edge_shift: torch.Tensor   # int32 (Ecap, 3) image shift s of every edge
+    ptr: torch.Tensor          # int64 (n+1,) node offsets
+    edge_ptr: torch.Tensor     # int64 (n+1,) edge offsets
+    batch: torch.Tensor        # int64 (Ncap,) graph id of every node
+    edge_vec: Optional[torch.Tensor]  # float32 (Ecap, 3) pos[src] - pos[dst] + s @ cell
+    cell: torch.Tensor         # (n, 3, 3) cells, stored dtype
+    shifts_needed: torch.Tensor  # int32 (n, 3) image layers needed, unclamped
+    node_extras: tuple         # ((values, offsets), ...)
+
+
 class ColumnStats(NamedTuple):
     """Per-column statistics of a variable, as :meth:`DDStore.column_stats`
     returns them. Column ``c`` is flat position ``c`` of a row (CSR: of an
@@ -1403,6 +1420,305 @@ class DDStore:
         if edge_vec and ke:
             vec_out.view(ecap, 3)[:edge_end] = torch.cat(vecs[:ke])
         return ptr, edge_ptr, edge_out, vec_out
+
+    # -------------------------------------------------- periodic radius graphs
+    def get_radius_graph_pbc_batch(
+        self,
+        pos_name: str,
+        cell_name: str,
+        indices: ArrayLike,
+        r: float,
+        *,
+        pbc: Sequence[bool] = (True, True, True),
+        max_shift: int = 3,
+        loop: bool = False,
+        pos_out: Optional[torch.Tensor] = None,
+        edge_out: Optional[torch.Tensor] = None,
+        batch_out: Optional[torch.Tensor] = None,
+        shift_out: Optional[torch.Tensor] = None,
+        vec_out: Optional[torch.Tensor] = None,
+        coo: bool = True,
+        edge_dtype: torch.dtype = torch.int64,
+        edge_fill: int = -1,
+        edge_vec: bool = False,
+        node_extras: Sequence[str] = (),
+    ) -> PeriodicGraphBatch:
+        """:meth:`get_radius_graph_batch` for periodic structures: the
+        neighbours of a node include the translated images of the other nodes
+        of its graph and of the node itself, and every edge carries its image
+        shift. Only positions and cells are stored and moved. On the GPU this
+        is one native call, with no host sync when the capacity buffers are
+        given.
+
+        ``pos_name`` is as for :meth:`get_radius_graph_batch`. ``cell_name``
+        is a fixed-stride variable with ``disp == 9``, float32 or float64
+        (anything else: ``TypeError``), with one row per graph (``ValueError``
+        otherwise): row ``g`` is the 3x3 cell of graph ``g``, lattice vector
+        ``a_k`` its elements ``3k..3k+2``. ``pbc`` is three bools for the
+        whole call, ``max_shift`` an int in ``1..8`` and ``r`` positive and
+        finite (``ValueError``). A full-rank cell is required whenever an axis
+        is periodic.
+
+        The rule is exact and the same on both backends; coordinates and cell
+        entries are taken as float32 and every operation is rounded to float32
+        on its own. Per graph and axis ``k`` (``i``, ``j`` the other two)::
+
+            q        = (f32(r) * |a_i x a_j|) / |det(cell)|
+            needed_k = floor(q * (1 + 2**-10)) + 1     # 0 if not pbc[k]
+            b_k      = min(max_shift, needed_k)
+
+        with ``a_i x a_j`` and ``det = (a_0 . (a_1 x a_2))`` in products,
+        differences and left-to-right sums; a zero-volume or non-finite cell
+        gives ``2**31 - 1``. ``needed_k`` is ``ceil(r / h_k)`` or one more for
+        the cell height ``h_k``: enough layers to see every neighbour within
+        ``r`` of nodes whose fractional coordinates lie in ``[0, 1)``. The
+        images are the integer triples ``s`` with ``|s_k| <= b_k``. For nodes
+        ``i``, ``j`` and image ``s``::
+
+            t_x = (f32(s0)*a0x + f32(s1)*a1x) + f32(s2)*a2x
+            dx  = (x_i - x_j) + t_x        # s == (0,0,0): dx = x_i - x_j
+            d2  = (dx*dx + dy*dy) + dz*dz
+
+        and ``(src=i, dst=j, shift=s)`` is an edge iff ``d2 <= f32(r)*f32(r)``
+        and (``i != j`` or ``s != 0`` or ``loop``): a node is a neighbour of
+        its own images, a NaN anywhere gives no edge. ``edge_vec`` is ``(dx,
+        dy, dz) = pos[src] - pos[dst] + s @ cell``, the ase convention. With
+        ``pbc=(False,) * 3`` the result is exactly that of
+        :meth:`get_radius_graph_batch`. A graph's edges are ordered by ``dst``,
+        then by shift (lexicographic in ``s0, s1, s2``, ascending), then by
+        ``src``. There is no ``max_neighbors``: the first ``K`` in that order
+        would favour the images on one side, and the ``K`` nearest are another
+        kernel.
+
+        ``pos``, ``edge_index``, ``ptr``, ``edge_ptr``, ``batch``, ``edge_vec``
+        and ``node_extras`` of the result, the buffers, kept prefixes,
+        ``edge_fill`` and the position variable's counters are as for
+        :meth:`get_radius_graph_batch`. Further
+
+        * ``edge_shift`` int32 ``(Ecap, 3)``: ``s`` in the row of its edge;
+          rows of no kept edge stay untouched, like ``edge_vec``;
+        * ``cell`` ``(n, 3, 3)`` in the stored dtype: exactly
+          ``get_batch(cell_name, indices)``; a bad index leaves its row
+          untouched and counts in the cell variable's ``oob_skipped`` (GPU
+          backend; the host's fixed-stride gather keeps no such counter);
+        * ``shifts_needed`` int32 ``(n, 3)``: ``needed_k``, not clamped by
+          ``max_shift``; 0 on non-periodic axes, for a bad index and for a
+          graph whose nodes were not kept. ``(shifts_needed >
+          max_shift).any()`` tells a truncated search.
+
+        Positions outside the cell are legal, but images beyond the box are
+        not searched: wrap first. ``shift_out`` (``3 * Ecap`` int32) joins
+        ``pos_out``, ``edge_out`` and ``batch_out`` (and ``vec_out`` with
+        ``edge_vec=True``): all or none."""
+        what = "get_radius_graph_pbc_batch"
+        self._refuse_mx(what, pos_name)
+        meta = self._meta(pos_name)
+        if (not meta["is_csr"] or meta["disp"] != 3
+                or meta["dtype"] not in (torch.float32, torch.float64)):
+            raise TypeError(
+                f"ddstore {what}: '{pos_name}' must be a CSR variable of float32 "
+                "or float64 with disp == 3")
+        cmeta = self._meta(cell_name)
+        if (cmeta["is_csr"] or "mx" in cmeta or cmeta["disp"] != 9
+                or cmeta["dtype"] not in (torch.float32, torch.float64)):
+            raise TypeError(
+                f"ddstore {what}: '{cell_name}' must be a fixed-stride variable of "
+                "float32 or float64 with disp == 9")
+        key = (cell_name, pos_name, "cell")
+        if key not in self._graph_extras_ok:  # once per pair of names
+            self._graph_extras_ok[key] = cmeta["nrows_total"] == meta["nrows_total"]
+        if not self._graph_extras_ok[key]:
+            raise ValueError(
+                f"ddstore {what}: '{cell_name}' must have one row per graph of "
+                f"'{pos_name}'")
+        rf = torch.tensor(float(r), dtype=torch.float32)
+        if not (bool(torch.isfinite(rf)) and float(rf) > 0.0):
+            raise ValueError(f"ddstore {what}: r must be positive and finite")
+        if int(max_shift) != max_shift or not 1 <= max_shift <= 8:
+            raise ValueError(f"ddstore {what}: max_shift must be an int in 1..8")
+        pbc = tuple(bool(p) for p in pbc)
+        if len(pbc) != 3:
+            raise ValueError(f"ddstore {what}: pbc is three bools")
+        if edge_dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"ddstore {what}: edge_dtype must be int32 or int64")
+        for nm in node_extras:
+            self._graph_extra(nm, pos_name)
+        bufs = (pos_out, edge_out, batch_out, shift_out) + ((vec_out,) if edge_vec else ())
+        if any(b is None for b in bufs) and not all(b is None for b in bufs):
+            raise ValueError(
+                f"ddstore {what}: pass pos_out, edge_out, batch_out, shift_out (and "
+                "vec_out with edge_vec=True) together")
+        if not edge_vec and vec_out is not None:
+            raise ValueError(f"ddstore {what}: vec_out needs edge_vec=True")
+        idx = torch.as_tensor(indices, dtype=torch.int64).flatten()
+        fill = int(torch.tensor([edge_fill], dtype=edge_dtype).item())
+        sized = pos_out is None
+        if sized:
+            # Ncap from the host offsets (a device `indices` syncs here); Ecap
+            # after the count
+            ih = idx.cpu()
+            ih = ih[(ih >= 0) & (ih < meta["nrows_total"])]
+            ncap = int((meta["goff"][ih + 1] - meta["goff"][ih]).sum())
+            pos_out = torch.empty((ncap, 3), dtype=meta["dtype"], device=self.device)
+            batch_out = torch.empty(ncap, dtype=torch.int64, device=self.device)
+            edge_out = torch.empty(0, dtype=edge_dtype, device=self.device)
+            shift_out = torch.empty(0, dtype=torch.int32, device=self.device)
+        else:
+            ncap = pos_out.numel() // 3
+            ecap = edge_out.numel() // 2
+            for buf, nm, dt, numel in (
+                    (batch_out, "batch_out", torch.int64, ncap),
+                    (edge_out, "edge_out", edge_dtype, 2 * ecap),
+                    (shift_out, "shift_out", torch.int32, 3 * ecap),
+                    (vec_out if edge_vec else None, "vec_out", torch.float32, 3 * ecap)):
+                if buf is not None and (
+                        buf.dtype != dt or not buf.is_contiguous()
+                        or buf.device != self.device or buf.numel() != numel):
+                    raise ValueError(
+                        f"ddstore {what}: {nm} must be a contiguous {dt} tensor of "
+                        f"{numel} elements on the store device (Ncap = {ncap} nodes, "
+                        f"Ecap = {ecap} edges)")
+        if vec_out is None:
+            vec_out = torch.empty(0, dtype=torch.float32, device=self.device)
+        if edge_dtype == torch.int32 and ncap >= 2 ** 31:
+            raise ValueError(f"ddstore {what}: int32 node ids need Ncap < 2**31")
+        idx = idx.to(self.device, non_blocking=True).contiguous()
+        self._account(meta, idx)
+        if self.mode == "hip":
+            self._account(cmeta, idx)
+            mask = sum(1 << k for k in range(3) if pbc[k])
+            ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed = (
+                self._backend.gather_radius_graph_pbc(
+                    pos_name, cell_name, idx, float(rf), mask, int(max_shift),
+                    bool(loop), pos_out, edge_out, batch_out, shift_out, vec_out,
+                    bool(edge_vec), sized, bool(coo), fill))
+        else:
+            ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed = (
+                self._radius_graph_pbc_host(
+                    pos_name, cell_name, idx, rf, pbc, int(max_shift), bool(loop),
+                    pos_out, edge_out, batch_out, shift_out, vec_out, bool(edge_vec),
+                    sized, bool(coo), fill))
+        ecap = edge_out.numel() // 2
+        return PeriodicGraphBatch(
+            pos_out, edge_out.view(2, ecap) if coo else edge_out.view(ecap, 2),
+            shift_out.view(ecap, 3), ptr, edge_ptr, batch_out.view(ncap),
+            vec_out.view(ecap, 3) if edge_vec else None, cell, needed,
+            tuple(self.get_csr(nm, idx) for nm in node_extras))
+
+    @staticmethod
+    def _pbc_layers(a: torch.Tensor, rf: torch.Tensor, pbc) -> list:
+        """``needed_k`` of one float32 (3, 3) cell by the documented rule,
+        every torch op one float32 rounding."""
+        needed = [0, 0, 0]
+        cross = []
+        for k in range(3):
+            u, v = a[(k + 1) % 3], a[(k + 2) % 3]
+            cross.append(torch.stack([u[1] * v[2] - u[2] * v[1],
+                                      u[2] * v[0] - u[0] * v[2],
+                                      u[0] * v[1] - u[1] * v[0]]))
+        c0 = cross[0]
+        adet = ((a[0, 0] * c0[0] + a[0, 1] * c0[1]) + a[0, 2] * c0[2]).abs()
+        for k in range(3):
+            if not pbc[k]:
+                continue
+            c = cross[k]
+            nrm = torch.sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2])
+            f = torch.floor(((rf * nrm) / adet) * torch.tensor(1.0009765625))
+            good = bool(adet > 0) and bool(torch.isfinite(adet)) and bool(f < 2.0 ** 30)
+            needed[k] = int(f) + 1 if good else 2 ** 31 - 1
+        return needed
+
+    def _radius_graph_pbc_host(self, pos_name, cell_name, idx, rf, pbc, max_shift,
+                               loop, pos_out, edge_out, batch_out, shift_out, vec_out,
+                               edge_vec, sized, coo, fill):
+        """Host path of :meth:`get_radius_graph_pbc_batch`: the two gathers,
+        then a brute force per kept graph over its image box in float32 torch
+        ops, each of which rounds on its own as the rule asks."""
+        meta = self._meta(pos_name)
+        n, ncap = idx.numel(), pos_out.numel() // 3
+        ok = (idx >= 0) & (idx < meta["nrows_total"])
+        safe = torch.where(ok, idx, torch.zeros_like(idx))
+        goff = meta["goff"]
+        lens = torch.where(ok, goff[safe + 1] - goff[safe], torch.zeros_like(idx))
+        ptr = torch.zeros(n + 1, dtype=torch.int64)
+        torch.cumsum(lens, 0, out=ptr[1:])
+        self._backend.gather_csr(pos_name, idx, ptr, pos_out, ncap)
+        # the host's fixed-stride gather refuses a bad index and has no
+        # counter for one: fetch the good rows, leave the others untouched
+        cell = torch.empty((n, 3, 3), dtype=self._meta(cell_name)["dtype"])
+        cell[ok] = self.get_batch(cell_name, idx[ok]).view(-1, 3, 3)
+        kn = int((ptr[1:] <= ncap).sum())  # ptr is monotone: a prefix is kept
+        node_end = int(ptr[kn])
+        batch = batch_out.view(ncap)
+        batch[node_end:] = n
+        batch[:node_end] = torch.repeat_interleave(
+            torch.arange(kn, dtype=torch.int64), lens[:kn])
+        r2 = rf * rf
+        p32 = pos_out.view(ncap, 3)[:node_end].to(torch.float32)
+        c32 = cell.to(torch.float32)
+        needed = torch.zeros((n, 3), dtype=torch.int32)
+        pairs, shifts, vecs = [], [], []
+        edge_ptr = torch.zeros(n + 1, dtype=torch.int64)
+        for s in range(kn):
+            if not bool(ok[s]):
+                continue
+            a = c32[s]
+            need = self._pbc_layers(a, rf, pbc)
+            needed[s] = torch.tensor(need, dtype=torch.int32)
+            b = [min(max_shift, v) for v in need]
+            S = torch.cartesian_prod(*(torch.arange(-v, v + 1) for v in b)).view(-1, 3)
+            Sf = S.to(torch.float32)
+            t = (Sf[:, 0:1] * a[0] + Sf[:, 1:2] * a[1]) + Sf[:, 2:3] * a[2]   # (nimg, 3)
+            zero = int((S == 0).all(1).nonzero())
+            p = p32[int(ptr[s]):int(ptr[s + 1])]
+            d = p[:, None, :] - p[None, :, :]         # d[i, j] = pos[i] - pos[j]
+
+            def vectors(img, src, dst):
+                dd = d[src, dst]
+                return torch.where((img == zero)[:, None], dd, dd + t[img])
+
+            nn, m = p.shape[0], []
+            ar = torch.arange(nn)
+            for m0 in range(0, S.shape[0], 16):       # m[img, src, dst], in chunks
+                img = torch.arange(m0, min(m0 + 16, S.shape[0]))
+                g = torch.meshgrid(img, ar, ar, indexing="ij")
+                v = vectors(*(x.reshape(-1) for x in g))
+                d2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+                m.append((d2 <= r2).view(img.numel(), nn, nn))
+            m = torch.cat(m)
+            if not loop:
+                m[zero].fill_diagonal_(False)
+            dst, img, src = m.permute(2, 0, 1).nonzero(as_tuple=True)  # dst, shift, src
+            edge_ptr[s + 1] = dst.numel()
+            pairs.append(torch.stack([src, dst], 1) + ptr[s])
+            shifts.append(S[img].to(torch.int32))
+            vecs.append(vectors(img, src, dst))
+        torch.cumsum(edge_ptr[1:].clone(), 0, out=edge_ptr[1:])
+        if sized:
+            total = int(edge_ptr[-1])
+            edge_out = torch.empty(2 * total, dtype=edge_out.dtype)
+            shift_out = torch.empty(3 * total, dtype=torch.int32)
+            if edge_vec:
+                vec_out = torch.empty(3 * total, dtype=torch.float32)
+        ecap = edge_out.numel() // 2
+        ke = min(kn, int((edge_ptr[1:] <= ecap).sum()))
+        edge_end = int(edge_ptr[ke])
+        # a bad index among the kept graphs appended nothing: cut by edges
+        kept = torch.cat(pairs + [torch.zeros((0, 2), dtype=torch.int64)])[:edge_end]
+        kept = kept.to(edge_out.dtype)
+        if coo:
+            ev = edge_out.view(2, ecap)
+            ev[:, edge_end:] = fill
+            ev[:, :edge_end] = kept.t()
+        else:
+            ev = edge_out.view(ecap, 2)
+            ev[edge_end:] = fill
+            ev[:edge_end] = kept
+        if edge_end:
+            shift_out.view(ecap, 3)[:edge_end] = torch.cat(shifts)[:edge_end]
+            if edge_vec:
+                vec_out.view(ecap, 3)[:edge_end] = torch.cat(vecs)[:edge_end]
+        return ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed
 
     def local_shard(self, name: str) -> torch.Tensor:
         """Zero-copy view of this rank's shard (rows x disp). Valid until
