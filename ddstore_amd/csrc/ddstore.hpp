@@ -962,12 +962,14 @@ public:
     // (ptr, edge_ptr, edge_out, vec_out); edge_ptr is [n+1], counts 0 edges
     // for a graph whose nodes were not kept and is otherwise unclamped. Every
     // element of batch_out and edge_out is written; vec_out only on rows of
-    // kept edges.
+    // kept edges. With `nearest`, max_neighbors (1..radius_nearest_max()) keeps
+    // every dst's nearest sources instead of its first ones: the select kernel
+    // stands for the count pass.
     std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gather_radius_graph(
         const std::string& pos_name, const at::Tensor& idx, double r,
         int64_t max_neighbors, bool loop, at::Tensor pos_out, at::Tensor edge_out,
         at::Tensor batch_out, at::Tensor vec_out, bool edge_vec, bool size_edges,
-        bool coo, int64_t edge_fill) {
+        bool coo, int64_t edge_fill, bool nearest) {
         RoctxRange rr_("ddstore::gather_radius_graph");
         DeviceVar& pv = var(pos_name);
         TORCH_CHECK(pv.is_csr, "ddstore gather_radius_graph: not a CSR variable");
@@ -981,6 +983,10 @@ public:
         TORCH_CHECK(std::isfinite(rf) && rf > 0.0f,
                     "ddstore gather_radius_graph: r must be positive and finite");
         const float r2 = rf * rf;
+        TORCH_CHECK(!nearest || (max_neighbors >= 1 &&
+                                 max_neighbors <= ddstore::radius_nearest_max()),
+                    "ddstore gather_radius_graph: the nearest cap is in 1..",
+                    ddstore::radius_nearest_max());
         const int64_t nidx = idx.numel();
         const int64_t ncap = pos_out.numel() / 3;
         TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
@@ -1000,9 +1006,14 @@ public:
         auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
         at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
         at::Tensor scratch = at::empty(
-            {(int64_t)ddstore::radius_scratch_bytes(nidx, ncap)}, bopts);
+            {(int64_t)ddstore::radius_scratch_bytes(nidx, ncap, nearest)}, bopts);
         if (nidx == 0) {
             edge_ptr.zero_();
+        } else if (nearest) {
+            ddstore::radius_nearest_select(
+                stream(), pos_out.data_ptr(), pv.dds_t, ptr.data_ptr<int64_t>(), nidx,
+                ncap, r2, (int)max_neighbors, loop, scratch.data_ptr(),
+                edge_ptr.data_ptr<int64_t>());
         } else {
             ddstore::radius_count(stream(), pos_out.data_ptr(), pv.dds_t,
                                   ptr.data_ptr<int64_t>(), nidx, ncap, r2, max_neighbors,
@@ -1039,7 +1050,7 @@ public:
             ddstore::radius_fill(stream(), pos_out.data_ptr(), pv.dds_t,
                                  ptr.data_ptr<int64_t>(), edge_ptr.data_ptr<int64_t>(),
                                  nidx, ncap, ecap, r2, loop, scratch.data_ptr(), out_t,
-                                 coo, edge_out.data_ptr(), d_vec);
+                                 coo, edge_out.data_ptr(), d_vec, nearest);
         ddstore::graph_fill(stream(), ptr.data_ptr<int64_t>(),
                             edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, out_t, coo,
                             edge_fill, batch_out.data_ptr<int64_t>(),
@@ -1057,7 +1068,8 @@ public:
     // buffers under size_edges. Returns (ptr, edge_ptr, edge_out, shift_out,
     // vec_out, cell, shifts_needed); shifts_needed is int32 (n, 3). shift_out
     // and vec_out are written only on rows of kept edges, a bad index leaves
-    // its cell row untouched.
+    // its cell row untouched. max_neighbors != 0 is the nearest cap (the caller
+    // has checked nodes * images < 2^32 for the variable).
     std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                at::Tensor>
     gather_radius_graph_pbc(const std::string& pos_name, const std::string& cell_name,
@@ -1065,7 +1077,8 @@ public:
                             int64_t max_shift, bool loop, at::Tensor pos_out,
                             at::Tensor edge_out, at::Tensor batch_out,
                             at::Tensor shift_out, at::Tensor vec_out, bool edge_vec,
-                            bool size_edges, bool coo, int64_t edge_fill) {
+                            bool size_edges, bool coo, int64_t edge_fill,
+                            int64_t max_neighbors) {
         RoctxRange rr_("ddstore::gather_radius_graph_pbc");
         const char* op = "ddstore gather_radius_graph_pbc: ";
         DeviceVar& pv = var(pos_name);
@@ -1086,6 +1099,10 @@ public:
         TORCH_CHECK(std::isfinite(rf) && rf > 0.0f, op, "r must be positive and finite");
         TORCH_CHECK(max_shift >= 1 && max_shift <= 8, op, "max_shift must be in 1..8");
         TORCH_CHECK(pbc >= 0 && pbc < 8, op, "pbc is a mask of three axes");
+        const bool nearest = max_neighbors != 0;
+        TORCH_CHECK(max_neighbors >= 0 && max_neighbors <= ddstore::radius_nearest_max(),
+                    op, "max_neighbors is 0 (none) or in 1..",
+                    ddstore::radius_nearest_max());
         const int64_t nidx = idx.numel();
         const int64_t ncap = pos_out.numel() / 3;
         TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
@@ -1108,9 +1125,17 @@ public:
         at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
         at::Tensor needed = at::empty({nidx, 3}, opts.dtype(at::kInt));
         at::Tensor scratch = at::empty(
-            {(int64_t)ddstore::radius_pbc_scratch_bytes(nidx)}, opts.dtype(at::kByte));
+            {(int64_t)ddstore::radius_pbc_scratch_bytes(nidx, ncap, nearest)},
+            opts.dtype(at::kByte));
         if (nidx == 0) {
             edge_ptr.zero_();
+        } else if (nearest) {
+            ddstore::radius_pbc_nearest_select(
+                stream(), pos_out.data_ptr(), pv.dds_t, cell.data_ptr(), cv.dds_t,
+                ptr.data_ptr<int64_t>(), idx.data_ptr<int64_t>(), nidx, pv.nrows_total(),
+                ncap, rf, (int)pbc, (int)max_shift, loop, (int)max_neighbors,
+                scratch.data_ptr(), edge_ptr.data_ptr<int64_t>(),
+                needed.data_ptr<int32_t>());
         } else {
             ddstore::radius_pbc_count(
                 stream(), pos_out.data_ptr(), pv.dds_t, cell.data_ptr(), cv.dds_t,
@@ -1155,7 +1180,7 @@ public:
                 stream(), pos_out.data_ptr(), pv.dds_t, ptr.data_ptr<int64_t>(),
                 edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, rf, (int)pbc, loop,
                 scratch.data_ptr(), out_t, coo, edge_out.data_ptr(),
-                shift_out.data_ptr<int32_t>(), d_vec);
+                shift_out.data_ptr<int32_t>(), d_vec, nearest);
         ddstore::graph_fill(stream(), ptr.data_ptr<int64_t>(),
                             edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, out_t, coo,
                             edge_fill, batch_out.data_ptr<int64_t>(),

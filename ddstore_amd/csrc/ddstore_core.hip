@@ -33,6 +33,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "ddstore_amd native core (MI355X / gfx950)";
     m.attr("MAX_PARTS") = DDS_MAX_PARTS;
     m.attr("RADIUS_TILE") = ddstore::radius_tile_nodes();
+    m.attr("RADIUS_NEAREST_MAX") = ddstore::radius_nearest_max();
     m.def("cycle_order", &ddstore::cycle_order,
           py::call_guard<py::gil_scoped_release>(),
           "Concatenated-cycle traversal of a permutation (order, starts)");

@@ -265,8 +265,19 @@ void graph_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_
 //
 // radius_tile_nodes: the nodes one LDS slice holds; larger graphs stream
 // through it (a second code path, for tests to aim at).
+//
+// Nearest mode (docs/API.md): with k in 1..radius_nearest_max() every dst
+// keeps its min(k, degree) edges of smallest key (d2 bits, src), still ordered
+// by src. radius_nearest_select stands for radius_count (same outputs; it
+// also leaves a threshold key per node in d_scratch; k out of range launches
+// nothing) and radius_fill takes nearest = true; both need
+// radius_scratch_bytes(nidx, ncap, true) bytes, 12 per node.
 int radius_tile_nodes();
-size_t radius_scratch_bytes(int64_t nidx, int64_t ncap);
+int radius_nearest_max();
+size_t radius_scratch_bytes(int64_t nidx, int64_t ncap, bool nearest = false);
+void radius_nearest_select(hipStream_t stream, const void* d_pos, int pos_t,
+                           const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r2,
+                           int k, bool loop, void* d_scratch, int64_t* d_edge_ptr);
 void radius_count(hipStream_t stream, const void* d_pos, int pos_t,
                   const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r2,
                   int64_t max_neighbors, bool loop, void* d_scratch,
@@ -275,7 +286,7 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
                  const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
                  int64_t ncap, int64_t ecap, float r2, bool loop,
                  const void* d_scratch, int out_t, bool coo, void* d_edge_out,
-                 float* d_vec_out);
+                 float* d_vec_out, bool nearest = false);
 
 // Periodic radius-graph fetch (DeviceStore::gather_radius_graph_pbc): as
 // above, with the translated images of every node. d_cell is the (nidx, 9)
@@ -302,7 +313,19 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
 // radius_pbc_fill: as radius_fill, and row d_edge_ptr[s] + e of the (ecap, 3)
 // int32 array d_shift_out is the edge's s. One launch; no atomics and no
 // counters in either.
-size_t radius_pbc_scratch_bytes(int64_t nidx);
+//
+// Nearest mode: as above with the key (d2 bits, image number * nodes + src),
+// the image number counting the box in shift order; every graph needs nodes *
+// images < 2^32, which the caller checks. radius_pbc_nearest_select stands
+// for radius_pbc_count, radius_pbc_fill takes nearest = true, and both need
+// radius_pbc_scratch_bytes(nidx, ncap, true) bytes.
+size_t radius_pbc_scratch_bytes(int64_t nidx, int64_t ncap = 0, bool nearest = false);
+void radius_pbc_nearest_select(hipStream_t stream, const void* d_pos, int pos_t,
+                               const void* d_cell, int cell_t, const int64_t* d_ptr,
+                               const int64_t* d_idx, int64_t nidx, int64_t nsamples,
+                               int64_t ncap, float r, int pbc, int max_shift, bool loop,
+                               int k, void* d_scratch, int64_t* d_edge_ptr,
+                               int32_t* d_needed);
 void radius_pbc_count(hipStream_t stream, const void* d_pos, int pos_t,
                       const void* d_cell, int cell_t, const int64_t* d_ptr,
                       const int64_t* d_idx, int64_t nidx, int64_t nsamples,
@@ -312,7 +335,7 @@ void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
                      const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
                      int64_t ncap, int64_t ecap, float r, int pbc, bool loop,
                      const void* d_scratch, int out_t, bool coo, void* d_edge_out,
-                     int32_t* d_shift_out, float* d_vec_out);
+                     int32_t* d_shift_out, float* d_vec_out, bool nearest = false);
 
 // MX (OCP microscaling v1.0) block-scaled storage. A variable of logical
 // width `disp` keeps each row packed as

@@ -1385,6 +1385,16 @@ __device__ __forceinline__ float radius_coord(Tin v) {
     else return v;
 }
 
+// The selection key of an edge in nearest mode: d2 by the rule (its bits order
+// as an unsigned integer, d2 >= 0) over the edge's position in its dst's run.
+// The select and fill passes form every key here, from the same dx, dy, dz.
+__device__ __forceinline__ uint64_t near_key(float dx, float dy, float dz,
+                                             uint32_t at) {
+#pragma clang fp contract(off)
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    return (uint64_t)__float_as_uint(d2) << 32 | at;
+}
+
 // Nodes [0, tn) of `p` (3 coordinates each) into the slice: consecutive
 // lanes read consecutive coordinates.
 template <typename Tin, int GROUP>
@@ -1563,13 +1573,15 @@ k_radius_scan(const int64_t* __restrict__ counts, int64_t nidx,
 // degree) at column edge_ptr[s] + e of a (2, ecap) output (COO) or at that row
 // of an (ecap, 2) one, both ids shifted by ptr[s]; with VEC row edge_ptr[s] + e
 // of vec is (dx, dy, dz) = pos[src] - pos[dst]. Nothing else is written: the
-// tail of the edge index is k_graph_fill's.
-template <typename Tin, typename Tout, int GROUP, bool COO, bool VEC>
+// tail of the edge index is k_graph_fill's. With NEAR a dst keeps the sources
+// whose key is <= thr[dst] (k_radius_nearest_select) instead of its first ones.
+template <typename Tin, typename Tout, int GROUP, bool COO, bool VEC, bool NEAR>
 __global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
 k_radius_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
               const int64_t* __restrict__ edge_ptr, int64_t nidx, int64_t ncap,
               int64_t ecap, float r2, bool loop, const int32_t* __restrict__ deg,
-              Tout* __restrict__ out, float* __restrict__ vec) {
+              const uint64_t* __restrict__ thr, Tout* __restrict__ out,
+              float* __restrict__ vec) {
     constexpr int GPB = kBlock / GROUP;
     __shared__ float s_pos[GPB * kRadiusSlice];
     float* sl = s_pos + (threadIdx.x / GROUP) * kRadiusSlice;
@@ -1593,9 +1605,11 @@ k_radius_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
             ctr.load(gp, n, cb, tid);
             int d[kRadiusCentres], w[kRadiusCentres] = {0, 0, 0, 0};
             int64_t start[kRadiusCentres];
+            uint64_t th[kRadiusCentres];  // NEAR: the centre's threshold key
 #pragma unroll
             for (int c = 0; c < kRadiusCentres; ++c) {
                 d[c] = ctr.j[c] < n ? deg[p0 + ctr.j[c]] : 0;
+                if constexpr (NEAR) th[c] = ctr.j[c] < n ? thr[p0 + ctr.j[c]] : 0;
                 int incl = d[c];
                 for (int off = 1; off < GROUP; off <<= 1) {
                     const int a = __shfl_up(incl, off, GROUP);
@@ -1608,6 +1622,9 @@ k_radius_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
                 sl, gp, n, staged, ctr, cb, tid, r2, loop,
                 [&](int c, int64_t src, float dx, float dy, float dz) {
                     if (w[c] >= d[c]) return;  // the K cap, and the reserved run
+                    if constexpr (NEAR) {
+                        if (near_key(dx, dy, dz, (uint32_t)src) > th[c]) return;
+                    }
                     const int64_t o = start[c] + w[c]++;
                     const Tout a = static_cast<Tout>(src + p0);
                     const Tout b = static_cast<Tout>(ctr.j[c] + p0);
@@ -1893,14 +1910,15 @@ k_radius_pbc_count(const Tin* __restrict__ pos, const Tcell* __restrict__ cell,
 // edge e of the graph (item order, then src ascending) at column edge_ptr[s] +
 // e of a (2, ecap) output (coo) or at that row of an (ecap, 2) one, both ids
 // shifted by ptr[s]; row edge_ptr[s] + e of shift is its image s and, with
-// VEC, that row of vec (dx, dy, dz). Nothing else is written.
-template <typename Tin, typename Tout, int GROUP, bool VEC>
+// VEC, that row of vec (dx, dy, dz). Nothing else is written. With NEAR an
+// edge is kept iff its key is <= thr[dst] (k_radius_nearest_select).
+template <typename Tin, typename Tout, int GROUP, bool VEC, bool NEAR>
 __global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
 k_radius_pbc_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
                   const int64_t* __restrict__ edge_ptr, int64_t nidx, int64_t ncap,
                   int64_t ecap, float r2, bool loop, const PbcBox* __restrict__ boxes,
-                  bool coo, Tout* __restrict__ out, int32_t* __restrict__ shift,
-                  float* __restrict__ vec) {
+                  const uint64_t* __restrict__ thr, bool coo, Tout* __restrict__ out,
+                  int32_t* __restrict__ shift, float* __restrict__ vec) {
     constexpr int GPB = kBlock / GROUP;
     __shared__ float s_pos[GPB * kRadiusSlice];
     float* sl = s_pos + (threadIdx.x / GROUP) * kRadiusSlice;
@@ -1927,8 +1945,30 @@ k_radius_pbc_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
             PbcItems<Tin, GROUP> it;
             it.load(gp, box, nimg, nitems, ib, tid);
             int d[kPbcItems] = {0, 0, 0, 0};
+            // NEAR: an item keeps the sources whose key (d2, image * n + src)
+            // is <= its dst's threshold, in both walks
+            uint64_t th[kPbcItems];
+            uint32_t at0[kPbcItems];  // key position of the item's source 0
+            if constexpr (NEAR) {
+#pragma unroll
+                for (int c = 0; c < kPbcItems; ++c) {
+                    th[c] = it.j[c] < n ? thr[p0 + it.j[c]] : 0;
+                    const int m = ((it.s[c][0] + box.b[0]) * (2 * box.b[1] + 1) +
+                                   (it.s[c][1] + box.b[1])) * (2 * box.b[2] + 1) +
+                                  (it.s[c][2] + box.b[2]);
+                    at0[c] = (uint32_t)m * (uint32_t)n;
+                }
+            }
+            auto keeps = [&](int c, int64_t src, float dx, float dy, float dz) {
+                if constexpr (NEAR)
+                    return near_key(dx, dy, dz, at0[c] + (uint32_t)src) <= th[c];
+                else
+                    return true;
+            };
             pbc_pass<Tin, GROUP>(sl, gp, n, staged, it, ib, nitems, tid, r2, loop,
-                                 [&](int c, int64_t, float, float, float) { ++d[c]; });
+                                 [&](int c, int64_t src, float dx, float dy, float dz) {
+                                     if (keeps(c, src, dx, dy, dz)) ++d[c];
+                                 });
             int64_t at[kPbcItems];  // next edge slot of each item
 #pragma unroll
             for (int c = 0; c < kPbcItems; ++c) {
@@ -1944,6 +1984,7 @@ k_radius_pbc_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
             pbc_pass<Tin, GROUP>(
                 sl, gp, n, staged, it, ib, nitems, tid, r2, loop,
                 [&](int c, int64_t src, float dx, float dy, float dz) {
+                    if (!keeps(c, src, dx, dy, dz)) return;
                     const int64_t o = at[c]++;
                     const Tout a = static_cast<Tout>(src + p0);
                     const Tout b = static_cast<Tout>(it.j[c] + p0);
@@ -1962,6 +2003,287 @@ k_radius_pbc_fill(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr,
                         vec[3 * o + 2] = dz;
                     }
                 });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Nearest-K cap of both radius fetches: every dst keeps the min(K, degree)
+// edges with the smallest key (d2, position in the dst's run), emitted in the
+// unchanged edge order (docs/API.md, "Radius graphs"). One kernel,
+// k_radius_nearest_select, stands where k_radius_count / k_radius_pbc_count
+// stand: per kept node the degree min(hits, K) and a 64-bit threshold, the
+// K-th smallest key of that dst (all ones when it has at most K hits), and
+// per graph counts[s] for k_radius_scan; the periodic form also leaves the
+// PbcBox and shifts_needed. The fill kernels (template flag NEAR) keep a hit
+// iff its key is <= the threshold. Keys are unique within a dst, so exactly K
+// pass; near_key forms them in both passes from the same dx, dy, dz.
+//
+// Mapping. The counting passes give a lane several dst and broadcast the
+// sources; K keys per dst in registers would spill there. Here a wave takes a
+// graph (positions in its LDS slice) and one dst at a time, and the dst's
+// candidates are spread over the lanes: candidate c = image m * n + src, 64
+// per round, so a 4-atom cell with 125 images fills the wave as a 200-atom
+// graph does. The dst position is wave-uniform; a lane steps (m, src) by 64
+// without dividing and decodes m to its shift with two exact multiply-shifts
+// (m < 17^3 < 2^13). Lanes whose candidate has d2 <= bound append its key to
+// the wave's LDS queue at ballot-prefix slots: no atomics. One dst per walk
+// of the slice: a block of dst would need a queue and a best list each, and
+// the LDS read of a candidate is not what a round costs.
+//
+// Selection. The best kNearGroup * kNearPer = 128 keys live sorted across the
+// lanes, element e = r * 64 + lane in register r. A flush sorts 128 queued
+// keys with a bitonic network (strides under 64 are lane shuffles, stride 64
+// is in-register), takes min(best[e], queue[127 - e]) (bitonic, and it holds
+// the 128 smallest of both) and sorts that with the seven stages of a
+// half-cleaner; then bound = d2 of the K-th key, so later rounds reject most
+// candidates with one compare. The queue holds 192 keys: until the first
+// flush it fills to more than K (<= 128) before a flush is due, and a round
+// adds up to 64. So a dst with at most K hits never sorts; its degree is the
+// queue length. After the first flush the queue is flushed at 64 keys.
+// kNearPer = 2 bounds K at 128 (RADIUS_NEAREST_MAX): what the models ask for
+// is 12 to 64, and a third register would make the network a 256-key one.
+//
+// The group is always a wave: at 16 lanes the best list would need 8 keys per
+// lane for the same bound and four times the stages per key, so small open
+// graphs (16 nodes: a quarter of the lanes busy per round) were left with the
+// wave; their rounds are few. A graph larger than the slice reads its
+// candidates from global memory (L2) instead of streaming tiles, which would
+// restage every tile once per dst. LDS: four slices and four queues are 18.1
+// KiB per block, 8 blocks per CU.
+//
+// Not tried: several dst per walk, a sort sized to the queue's fill, the
+// first-flush threshold below 64, sub-wave groups, an image loop outside the
+// lanes for large cells.
+//
+// Measured on MI355X (profiles/radius_nearest_ab.txt), K = 12 / 32, int64 ids,
+// into Ncap * K edge slots. 8,192 graphs of 16..239 nodes: 1.82 / 1.29 ms per
+// fetch against 4.46 / 4.48 ms for the uncapped fetch with edge vectors plus a
+// torch thinning (K = 12 drops 2.6 M of 13.25 M edges, so many dst sort; K =
+// 32 drops 269 and almost none does).
+// 8,192 periodic structures of 2..64 atoms: 2.61 / 2.44 ms against 2.58 /
+// 2.60 ms, no win: one dst per walk and a decoded image per candidate cost
+// what the discarded edges save. The per-kernel split was not measured; the
+// whole-call difference to the uncapped fetch is 4.7 to 7.9 ps per candidate
+// test, next to 11.1 ps (open) and 3.2 ps (periodic) of the counting passes.
+// The select kernel uses 60 (periodic: 83) VGPRs and no scratch.
+// ---------------------------------------------------------------------------
+
+constexpr int kNearGroup = 64;  // lanes per graph of the select kernel: a wave
+constexpr int kNearPer = 2;     // best keys a lane holds
+constexpr int kNearBest = kNearGroup * kNearPer;
+constexpr int kNearQueue = kNearBest + kNearGroup;
+constexpr uint64_t kNearNone = ~0ull;  // above every key: d2 <= r2 is finite
+
+// One compare-exchange stage at distance J of a bitonic network over the keys
+// v, element e = r * kNearGroup + lane; blocks of BLOCK elements alternate
+// direction (BLOCK = kNearBest: all ascending).
+template <int J, int BLOCK>
+__device__ __forceinline__ void near_stage(uint64_t (&v)[kNearPer], int lane) {
+    if constexpr (J >= kNearGroup) {
+        constexpr int jr = J / kNearGroup;
+#pragma unroll
+        for (int r = 0; r < kNearPer; ++r) {
+            if (r & jr) continue;
+            const bool asc = ((r * kNearGroup + lane) & BLOCK) == 0 || BLOCK == kNearBest;
+            const uint64_t lo = v[r] < v[r | jr] ? v[r] : v[r | jr];
+            const uint64_t hi = v[r] < v[r | jr] ? v[r | jr] : v[r];
+            v[r] = asc ? lo : hi;
+            v[r | jr] = asc ? hi : lo;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < kNearPer; ++r) {
+            const uint64_t p = __shfl_xor((unsigned long long)v[r], J, kNearGroup);
+            const bool asc = ((r * kNearGroup + lane) & BLOCK) == 0 || BLOCK == kNearBest;
+            const bool low = (lane & J) == 0;
+            v[r] = (low == asc) == (v[r] < p) ? v[r] : p;
+        }
+    }
+}
+
+template <int BLOCK, int J = BLOCK / 2>
+__device__ __forceinline__ void near_merge(uint64_t (&v)[kNearPer], int lane) {
+    near_stage<J, BLOCK>(v, lane);
+    if constexpr (J > 1) near_merge<BLOCK, J / 2>(v, lane);
+}
+
+template <int BLOCK = 2>
+__device__ __forceinline__ void near_sort(uint64_t (&v)[kNearPer], int lane) {
+    near_merge<BLOCK>(v, lane);
+    if constexpr (BLOCK < kNearBest) near_sort<2 * BLOCK>(v, lane);
+}
+
+// The queue's keys [0, qn) into the sorted best list, 128 at a time.
+__device__ __forceinline__ void near_flush(const uint64_t* q, int qn,
+                                           uint64_t (&best)[kNearPer], int lane) {
+    for (int base = 0; base < qn; base += kNearBest) {
+        uint64_t v[kNearPer];
+#pragma unroll
+        for (int r = 0; r < kNearPer; ++r) {
+            const int e = base + r * kNearGroup + lane;
+            v[r] = e < qn ? q[e] : kNearNone;
+        }
+        near_sort(v, lane);
+#pragma unroll
+        for (int r = 0; r < kNearPer; ++r) {  // element 127 - e of the queue
+            const uint64_t o = __shfl((unsigned long long)v[kNearPer - 1 - r],
+                                      kNearGroup - 1 - lane, kNearGroup);
+            best[r] = best[r] < o ? best[r] : o;
+        }
+        near_merge<kNearBest>(best, lane);
+    }
+}
+
+// Degree, threshold and per-graph count in nearest mode (see the section
+// note). deg[ptr[s] + j] = min(hits of dst j, K) and thr[ptr[s] + j] for every
+// kept graph; every counts[s] is written. PBC: the box, shifts_needed and the
+// kept test of k_radius_pbc_count, `cell`, `idx`, `boxes` and `needed_out` as
+// there; without it they are unused and the only image is the zero one.
+template <typename Tin, typename Tcell, bool PBC>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_radius_nearest_select(const Tin* __restrict__ pos, const Tcell* __restrict__ cell,
+                        const int64_t* __restrict__ ptr, const int64_t* __restrict__ idx,
+                        int64_t nidx, int64_t nsamples, int64_t ncap, float rf, float r2,
+                        int pbc, int max_shift, bool loop, int K,
+                        int64_t* __restrict__ counts, PbcBox* __restrict__ boxes,
+                        int32_t* __restrict__ needed_out, int32_t* __restrict__ deg,
+                        uint64_t* __restrict__ thr) {
+#pragma clang fp contract(off)
+    constexpr int GPB = kBlock / kNearGroup;
+    __shared__ float s_pos[GPB * kRadiusSlice];
+    __shared__ uint64_t s_queue[GPB * kNearQueue];
+    float* sl = s_pos + (threadIdx.x / kNearGroup) * kRadiusSlice;
+    uint64_t* q = s_queue + (threadIdx.x / kNearGroup) * kNearQueue;
+    const int tid = threadIdx.x % kNearGroup;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / kNearGroup; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        const int64_t n = p1 - p0;
+        bool kept = p0 >= 0 && p1 <= ncap;
+        PbcBox box = {};
+        int needed[3] = {0, 0, 0};
+        if constexpr (PBC) {
+            const int64_t g = idx[s];
+            kept = kept && g >= 0 && g < nsamples;
+            if (kept) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) box.a[k] = radius_coord(cell[9 * s + k]);
+                pbc_layers(box.a, rf, pbc, needed);
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    box.b[k] = needed[k] < max_shift ? needed[k] : max_shift;
+                if (tid == 0) boxes[s] = box;
+            }
+        }
+        int64_t total = 0;
+        if (kept && n > 0) {
+            const uint32_t n1 = 2 * box.b[1] + 1, n2 = 2 * box.b[2] + 1;
+            const int64_t ncand = n * ((2 * box.b[0] + 1) * (int)(n1 * n2));
+            // x / d = (x * mg) >> 20 for x < 2^13, d <= 17
+            const uint32_t mg1 = (1u << 20) / n1 + 1, mg2 = (1u << 20) / n2 + 1;
+            const Tin* __restrict__ gp = pos + 3 * p0;
+            const bool staged = n <= kRadiusTile;
+            if (staged) {
+                group_lds_sync();  // the graph before is done with the slice
+                radius_stage<Tin, kNearGroup>(sl, gp, (int)n, tid);
+                group_lds_sync();
+            }
+            // the lane's first candidate, and its step of one round
+            const int64_t m0 = tid / n, src0 = tid - m0 * n;
+            const int64_t mstep = kNearGroup / n, sstep = kNearGroup - mstep * n;
+            for (int64_t j = 0; j < n; ++j) {
+                float xj, yj, zj;
+                if (staged) {
+                    xj = sl[j], yj = sl[kRadiusTile + j], zj = sl[2 * kRadiusTile + j];
+                } else {
+                    xj = radius_coord(gp[3 * j]);
+                    yj = radius_coord(gp[3 * j + 1]);
+                    zj = radius_coord(gp[3 * j + 2]);
+                }
+                uint64_t best[kNearPer];
+#pragma unroll
+                for (int r = 0; r < kNearPer; ++r) best[r] = kNearNone;
+                float bound = r2;
+                uint64_t kth = kNearNone;  // the K-th smallest key once there are more
+                int qn = 0;
+                bool flushed = false;
+                int64_t m = m0, src = src0;
+                for (int64_t c0 = 0; c0 < ncand; c0 += kNearGroup) {
+                    const bool in = c0 + tid < ncand;
+                    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+                    bool hit = false;
+                    if (in) {
+                        if (staged) {
+                            dx = sl[src] - xj;
+                            dy = sl[kRadiusTile + src] - yj;
+                            dz = sl[2 * kRadiusTile + src] - zj;
+                        } else {
+                            dx = radius_coord(gp[3 * src]) - xj;
+                            dy = radius_coord(gp[3 * src + 1]) - yj;
+                            dz = radius_coord(gp[3 * src + 2]) - zj;
+                        }
+                        bool zero = true;
+                        if constexpr (PBC) {
+                            const uint32_t mm = (uint32_t)m;
+                            const uint32_t m01 = mm * mg2 >> 20, i0 = m01 * mg1 >> 20;
+                            const int s0 = (int)i0 - box.b[0];
+                            const int s1 = (int)(m01 - i0 * n1) - box.b[1];
+                            const int s2 = (int)(mm - m01 * n2) - box.b[2];
+                            zero = (s0 | s1 | s2) == 0;
+                            if (!zero) {
+                                const float f0 = (float)s0, f1 = (float)s1, f2 = (float)s2;
+                                dx = dx + ((f0 * box.a[0] + f1 * box.a[3]) + f2 * box.a[6]);
+                                dy = dy + ((f0 * box.a[1] + f1 * box.a[4]) + f2 * box.a[7]);
+                                dz = dz + ((f0 * box.a[2] + f1 * box.a[5]) + f2 * box.a[8]);
+                            }
+                        }
+                        const float d2 = (dx * dx + dy * dy) + dz * dz;
+                        hit = d2 <= bound && (loop || !zero || src != j);
+                    }
+                    const uint64_t mask = __ballot(hit);
+                    if (hit)
+                        q[qn + __popcll(mask & ((1ull << tid) - 1))] =
+                            near_key(dx, dy, dz, (uint32_t)(c0 + tid));
+                    qn += __popcll(mask);
+                    src += sstep;
+                    m += mstep;
+                    if (src >= n) {
+                        src -= n;
+                        ++m;
+                    }
+                    // at most 128 keys wait here before a round (K <= 128), so
+                    // the round's 64 fit; nothing is sorted while qn <= K
+                    const bool last = c0 + kNearGroup >= ncand;
+                    if (flushed ? (qn >= kNearGroup || (last && qn > 0))
+                                : (qn > K && (qn >= kNearGroup || last))) {
+                        group_lds_sync();
+                        near_flush(q, qn, best, tid);
+                        group_lds_sync();
+                        uint64_t at_k = best[0];  // the register of element K - 1
+#pragma unroll
+                        for (int r = 1; r < kNearPer; ++r)
+                            if ((K - 1) / kNearGroup == r) at_k = best[r];
+                        kth = __shfl((unsigned long long)at_k, (K - 1) % kNearGroup,
+                                     kNearGroup);
+                        bound = __uint_as_float((uint32_t)(kth >> 32));
+                        flushed = true;
+                        qn = 0;
+                    }
+                }
+                if (tid == 0) {
+                    thr[p0 + j] = kth;
+                    deg[p0 + j] = flushed ? K : qn;
+                }
+                total += flushed ? K : qn;
+            }
+        }
+        if (tid == 0) {
+            counts[s] = total;
+            if constexpr (PBC) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) needed_out[3 * s + k] = needed[k];
+            }
         }
     }
 }
@@ -2791,8 +3113,12 @@ void graph_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_
 
 int radius_tile_nodes() { return kRadiusTile; }
 
-size_t radius_scratch_bytes(int64_t nidx, int64_t ncap) {
-    return (size_t)(nidx + 1) * 8 + (size_t)(ncap + 1) * 4;
+int radius_nearest_max() { return kNearBest; }
+
+// Scratch of the open call: counts, then in nearest mode the thresholds, then
+// the degrees.
+size_t radius_scratch_bytes(int64_t nidx, int64_t ncap, bool nearest) {
+    return (size_t)(nidx + 1) * 8 + (size_t)(ncap + 1) * (nearest ? 12 : 4);
 }
 
 namespace {
@@ -2844,23 +3170,51 @@ void radius_count(hipStream_t stream, const void* d_pos, int pos_t,
                        d_edge_ptr);
 }
 
+void radius_nearest_select(hipStream_t stream, const void* d_pos, int pos_t,
+                           const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r2,
+                           int k, bool loop, void* d_scratch, int64_t* d_edge_ptr) {
+    if (nidx == 0 || k < 1 || k > kNearBest) return;
+    int64_t* counts = reinterpret_cast<int64_t*>(d_scratch);
+    uint64_t* thr = reinterpret_cast<uint64_t*>(counts + nidx + 1);
+    int32_t* deg = reinterpret_cast<int32_t*>(thr + ncap + 1);
+    const int grid = radius_grid(nidx, kNearGroup);
+    auto launch = [&](auto ti) {
+        using Tin = typename decltype(ti)::type;
+        hipLaunchKernelGGL((k_radius_nearest_select<Tin, float, false>), dim3(grid),
+                           dim3(kBlock), 0, stream, (const Tin*)d_pos,
+                           (const float*)nullptr, d_ptr, (const int64_t*)nullptr, nidx,
+                           (int64_t)0, ncap, 0.0f, r2, 0, 0, loop, k, counts,
+                           (PbcBox*)nullptr, (int32_t*)nullptr, deg, thr);
+    };
+    if (pos_t == DDS_F64) launch(TypeTag<double>{});
+    else if (pos_t == DDS_F32) launch(TypeTag<float>{});
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, counts, nidx,
+                       d_edge_ptr);
+}
+
 void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
                  const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
                  int64_t ncap, int64_t ecap, float r2, bool loop,
                  const void* d_scratch, int out_t, bool coo, void* d_edge_out,
-                 float* d_vec_out) {
+                 float* d_vec_out, bool nearest) {
     if (nidx == 0 || ecap == 0) return;
+    const int64_t* after_counts = reinterpret_cast<const int64_t*>(d_scratch) + nidx + 1;
+    const uint64_t* thr = reinterpret_cast<const uint64_t*>(after_counts);
     const int32_t* deg = reinterpret_cast<const int32_t*>(
-        reinterpret_cast<const int64_t*>(d_scratch) + nidx + 1);
+        nearest ? after_counts + ncap + 1 : after_counts);
     const int group = radius_group(nidx, ncap);
     const int grid = radius_grid(nidx, group);
     auto launch = [&](auto ti, auto to, auto G, auto c, auto v) {
         using Tin = typename decltype(ti)::type;
         using Tout = typename decltype(to)::type;
-        hipLaunchKernelGGL(
-            (k_radius_fill<Tin, Tout, G(), decltype(c)::value, decltype(v)::value>),
-            dim3(grid), dim3(kBlock), 0, stream, (const Tin*)d_pos, d_ptr, d_edge_ptr,
-            nidx, ncap, ecap, r2, loop, deg, (Tout*)d_edge_out, d_vec_out);
+        constexpr bool C = decltype(c)::value, V = decltype(v)::value;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, stream,
+                               (const Tin*)d_pos, d_ptr, d_edge_ptr, nidx, ncap, ecap, r2,
+                               loop, deg, thr, (Tout*)d_edge_out, d_vec_out);
+        };
+        if (nearest) go(k_radius_fill<Tin, Tout, G(), C, V, true>);
+        else go(k_radius_fill<Tin, Tout, G(), C, V, false>);
     };
     auto launch_flags = [&](auto ti, auto to, auto G) {
         if (coo && d_vec_out) launch(ti, to, G, std::true_type{}, std::true_type{});
@@ -2878,8 +3232,11 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
     });
 }
 
-size_t radius_pbc_scratch_bytes(int64_t nidx) {
-    return (size_t)(nidx + 1) * (8 + sizeof(PbcBox));
+// Scratch of the periodic call: counts, the boxes, then in nearest mode the
+// thresholds and the degrees of ncap nodes.
+size_t radius_pbc_scratch_bytes(int64_t nidx, int64_t ncap, bool nearest) {
+    return (size_t)(nidx + 1) * (8 + sizeof(PbcBox)) +
+           (nearest ? (size_t)(ncap + 1) * 12 : 0);
 }
 
 namespace {
@@ -2931,23 +3288,60 @@ void radius_pbc_count(hipStream_t stream, const void* d_pos, int pos_t,
                        d_edge_ptr);
 }
 
+void radius_pbc_nearest_select(hipStream_t stream, const void* d_pos, int pos_t,
+                               const void* d_cell, int cell_t, const int64_t* d_ptr,
+                               const int64_t* d_idx, int64_t nidx, int64_t nsamples,
+                               int64_t ncap, float r, int pbc, int max_shift, bool loop,
+                               int k, void* d_scratch, int64_t* d_edge_ptr,
+                               int32_t* d_needed) {
+    if (nidx == 0 || k < 1 || k > kNearBest) return;
+    int64_t* counts = reinterpret_cast<int64_t*>(d_scratch);
+    PbcBox* boxes = reinterpret_cast<PbcBox*>(counts + nidx + 1);
+    uint64_t* thr = reinterpret_cast<uint64_t*>(boxes + nidx + 1);
+    int32_t* deg = reinterpret_cast<int32_t*>(thr + ncap + 1);
+    const int grid = radius_grid(nidx, kNearGroup);
+    auto launch = [&](auto ti, auto tc) {
+        using Tin = typename decltype(ti)::type;
+        using Tcell = typename decltype(tc)::type;
+        hipLaunchKernelGGL((k_radius_nearest_select<Tin, Tcell, true>), dim3(grid),
+                           dim3(kBlock), 0, stream, (const Tin*)d_pos,
+                           (const Tcell*)d_cell, d_ptr, d_idx, nidx, nsamples, ncap, r,
+                           r * r, pbc, max_shift, loop, k, counts, boxes, d_needed, deg,
+                           thr);
+    };
+    auto launch_cell = [&](auto ti) {
+        if (cell_t == DDS_F64) launch(ti, TypeTag<double>{});
+        else if (cell_t == DDS_F32) launch(ti, TypeTag<float>{});
+    };
+    if (pos_t == DDS_F64) launch_cell(TypeTag<double>{});
+    else if (pos_t == DDS_F32) launch_cell(TypeTag<float>{});
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, counts, nidx,
+                       d_edge_ptr);
+}
+
 void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
                      const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
                      int64_t ncap, int64_t ecap, float r, int pbc, bool loop,
                      const void* d_scratch, int out_t, bool coo, void* d_edge_out,
-                     int32_t* d_shift_out, float* d_vec_out) {
+                     int32_t* d_shift_out, float* d_vec_out, bool nearest) {
     if (nidx == 0 || ecap == 0) return;
     const PbcBox* boxes = reinterpret_cast<const PbcBox*>(
         reinterpret_cast<const int64_t*>(d_scratch) + nidx + 1);
+    const uint64_t* thr = reinterpret_cast<const uint64_t*>(boxes + nidx + 1);
     const int group = radius_pbc_group(nidx, ncap, pbc);
     const int grid = radius_grid(nidx, group);
     auto launch = [&](auto ti, auto to, auto G, auto v) {
         using Tin = typename decltype(ti)::type;
         using Tout = typename decltype(to)::type;
-        hipLaunchKernelGGL((k_radius_pbc_fill<Tin, Tout, G(), decltype(v)::value>),
-                           dim3(grid), dim3(kBlock), 0, stream, (const Tin*)d_pos, d_ptr,
-                           d_edge_ptr, nidx, ncap, ecap, r * r, loop, boxes, coo,
-                           (Tout*)d_edge_out, d_shift_out, d_vec_out);
+        constexpr bool V = decltype(v)::value;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, stream,
+                               (const Tin*)d_pos, d_ptr, d_edge_ptr, nidx, ncap, ecap,
+                               r * r, loop, boxes, thr, coo, (Tout*)d_edge_out,
+                               d_shift_out, d_vec_out);
+        };
+        if (nearest) go(k_radius_pbc_fill<Tin, Tout, G(), V, true>);
+        else go(k_radius_pbc_fill<Tin, Tout, G(), V, false>);
     };
     auto launch_out = [&](auto ti, auto G) {
         auto with_vec = [&](auto to) {

@@ -1219,6 +1219,7 @@ class DDStore:
         r: float,
         *,
         max_neighbors: Optional[int] = None,
+        nearest: bool = False,
         loop: bool = False,
         pos_out: Optional[torch.Tensor] = None,
         edge_out: Optional[torch.Tensor] = None,
@@ -1256,6 +1257,16 @@ class DDStore:
         ``max_neighbors=K`` every ``dst`` keeps its first ``K`` sources in
         that order -- the lowest node ids, deterministic, NOT the ``K``
         nearest.
+
+        With ``nearest=True`` (``max_neighbors`` is then required and an int
+        in ``1 .. _C.RADIUS_NEAREST_MAX``, ``ValueError`` otherwise) every
+        ``dst`` keeps its ``K`` nearest sources instead: its edges are ranked
+        by the key ``(d2, src)``, ``d2`` the float32 above, the ``min(K,
+        degree)`` smallest keys are kept and emitted in the unchanged order,
+        by ``src``, not by distance. Equal distances go to the lower ``src``,
+        the same on both backends. With ``K >=`` every degree the result is
+        that of the uncapped call, and ``edge_ptr[-1] <= kept nodes * K``, so
+        ``Ecap = Ncap * K`` always suffices.
 
         With ``n = len(indices)`` the result holds
 
@@ -1298,6 +1309,8 @@ class DDStore:
         if max_neighbors is not None and (
                 int(max_neighbors) != max_neighbors or max_neighbors < 1):
             raise ValueError(f"ddstore {what}: max_neighbors must be None or an int >= 1")
+        if nearest:
+            self._check_nearest(what, max_neighbors, pos_name, 1)
         if edge_dtype not in (torch.int32, torch.int64):
             raise TypeError(f"ddstore {what}: edge_dtype must be int32 or int64")
         for nm in node_extras:
@@ -1349,11 +1362,11 @@ class DDStore:
         if self.mode == "hip":
             ptr, edge_ptr, edge_out, vec_out = self._backend.gather_radius_graph(
                 pos_name, idx, float(rf), k, bool(loop), pos_out, edge_out, batch_out,
-                vec_out, bool(edge_vec), sized, bool(coo), fill)
+                vec_out, bool(edge_vec), sized, bool(coo), fill, bool(nearest))
         else:
             ptr, edge_ptr, edge_out, vec_out = self._radius_graph_host(
                 pos_name, idx, rf, k, bool(loop), pos_out, edge_out, batch_out,
-                vec_out, bool(edge_vec), sized, bool(coo), fill)
+                vec_out, bool(edge_vec), sized, bool(coo), fill, bool(nearest))
         ecap = edge_out.numel() // 2
         return RadiusGraphBatch(
             pos_out, edge_out.view(2, ecap) if coo else edge_out.view(ecap, 2),
@@ -1361,8 +1374,37 @@ class DDStore:
             vec_out.view(ecap, 3) if edge_vec else None,
             tuple(self.get_csr(nm, idx) for nm in node_extras))
 
+    def _check_nearest(self, what, k, name, images):
+        """The nearest cap's ``K``, and once per variable and image count that
+        the 32-bit tie-break holds every position of a dst's run."""
+        from . import _C
+
+        if (k is None or isinstance(k, bool) or int(k) != k
+                or not 1 <= k <= _C.RADIUS_NEAREST_MAX):
+            raise ValueError(
+                f"ddstore {what}: the nearest cap needs max_neighbors, an int in "
+                f"1..{_C.RADIUS_NEAREST_MAX}")
+        key = (name, "nearest", images)
+        if key not in self._graph_extras_ok:
+            goff = self._meta(name)["goff"]
+            most = int((goff[1:] - goff[:-1]).max()) if goff.numel() > 1 else 0
+            self._graph_extras_ok[key] = most * images < 2 ** 32
+        if not self._graph_extras_ok[key]:
+            raise ValueError(
+                f"ddstore {what}: the nearest cap ranks at most 2**32 - 1 candidates "
+                "(nodes x images) per dst")
+
+    @staticmethod
+    def _thin_nearest(m: torch.Tensor, d2: torch.Tensor, k: int) -> torch.Tensor:
+        """``m[dst, position]`` cut to every row's ``k`` smallest ``(d2,
+        position)``: a stable sort on the float32 ``d2`` of the rule."""
+        order = torch.sort(torch.where(m, d2, torch.full_like(d2, float("inf"))),
+                           dim=1, stable=True).indices[:, :k]
+        return m & torch.zeros_like(m).scatter_(1, order, True)
+
     def _radius_graph_host(self, pos_name, idx, rf, k, loop, pos_out, edge_out,
-                           batch_out, vec_out, edge_vec, sized, coo, fill):
+                           batch_out, vec_out, edge_vec, sized, coo, fill,
+                           nearest=False):
         """Host path of :meth:`get_radius_graph_batch`: the CSR gather, then a
         brute force per kept graph in float32 torch ops, each of which rounds
         on its own as the rule asks."""
@@ -1392,7 +1434,9 @@ class DDStore:
             m = (d2 <= r2).t()                        # m[dst, src]
             if not loop:
                 m.fill_diagonal_(False)
-            if k:
+            if k and nearest:
+                m = self._thin_nearest(m, d2.t(), k)  # the k nearest sources per dst
+            elif k:
                 m &= torch.cumsum(m, 1) <= k          # the first k sources per dst
             dst, src = m.nonzero(as_tuple=True)       # by dst, then src
             edge_ptr[s + 1] = dst.numel()
@@ -1431,6 +1475,7 @@ class DDStore:
         *,
         pbc: Sequence[bool] = (True, True, True),
         max_shift: int = 3,
+        max_neighbors: Optional[int] = None,
         loop: bool = False,
         pos_out: Optional[torch.Tensor] = None,
         edge_out: Optional[torch.Tensor] = None,
@@ -1486,9 +1531,20 @@ class DDStore:
         ``pbc=(False,) * 3`` the result is exactly that of
         :meth:`get_radius_graph_batch`. A graph's edges are ordered by ``dst``,
         then by shift (lexicographic in ``s0, s1, s2``, ascending), then by
-        ``src``. There is no ``max_neighbors``: the first ``K`` in that order
-        would favour the images on one side, and the ``K`` nearest are another
-        kernel.
+        ``src``.
+
+        ``max_neighbors=K`` (an int in ``1 .. _C.RADIUS_NEAREST_MAX``,
+        ``ValueError`` otherwise) is the nearest cap of
+        :meth:`get_radius_graph_batch` with ``nearest=True``; there is no
+        first-``K`` cap here, which would favour the images on one side. Every
+        ``dst`` keeps the ``min(K, degree)`` edges with the smallest key
+        ``(d2, position of the edge in the dst's run)``, so equal distances
+        go to the lower shift, then the lower ``src``; the kept edges stay in
+        the order above and everything below counts the thinned runs.
+        ``edge_ptr[-1] <= kept nodes * K``: ``Ecap = Ncap * K`` always
+        suffices. The position is ranked in 32 bits, so a variable whose
+        largest graph has ``nodes * (2*max_shift+1)**3 >= 2**32`` is refused
+        (``ValueError``).
 
         ``pos``, ``edge_index``, ``ptr``, ``edge_ptr``, ``batch``, ``edge_vec``
         and ``node_extras`` of the result, the buffers, kept prefixes,
@@ -1539,6 +1595,10 @@ class DDStore:
         pbc = tuple(bool(p) for p in pbc)
         if len(pbc) != 3:
             raise ValueError(f"ddstore {what}: pbc is three bools")
+        if max_neighbors is not None:
+            self._check_nearest(what, max_neighbors, pos_name,
+                                (2 * int(max_shift) + 1) ** 3)
+        k = int(max_neighbors) if max_neighbors is not None else 0
         if edge_dtype not in (torch.int32, torch.int64):
             raise TypeError(f"ddstore {what}: edge_dtype must be int32 or int64")
         for nm in node_extras:
@@ -1591,13 +1651,13 @@ class DDStore:
                 self._backend.gather_radius_graph_pbc(
                     pos_name, cell_name, idx, float(rf), mask, int(max_shift),
                     bool(loop), pos_out, edge_out, batch_out, shift_out, vec_out,
-                    bool(edge_vec), sized, bool(coo), fill))
+                    bool(edge_vec), sized, bool(coo), fill, k))
         else:
             ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed = (
                 self._radius_graph_pbc_host(
                     pos_name, cell_name, idx, rf, pbc, int(max_shift), bool(loop),
                     pos_out, edge_out, batch_out, shift_out, vec_out, bool(edge_vec),
-                    sized, bool(coo), fill))
+                    sized, bool(coo), fill, k))
         ecap = edge_out.numel() // 2
         return PeriodicGraphBatch(
             pos_out, edge_out.view(2, ecap) if coo else edge_out.view(ecap, 2),
@@ -1630,7 +1690,7 @@ class DDStore:
 
     def _radius_graph_pbc_host(self, pos_name, cell_name, idx, rf, pbc, max_shift,
                                loop, pos_out, edge_out, batch_out, shift_out, vec_out,
-                               edge_vec, sized, coo, fill):
+                               edge_vec, sized, coo, fill, k=0):
         """Host path of :meth:`get_radius_graph_pbc_batch`: the two gathers,
         then a brute force per kept graph over its image box in float32 torch
         ops, each of which rounds on its own as the rule asks."""
@@ -1677,7 +1737,7 @@ class DDStore:
                 dd = d[src, dst]
                 return torch.where((img == zero)[:, None], dd, dd + t[img])
 
-            nn, m = p.shape[0], []
+            nn, m, dist = p.shape[0], [], []
             ar = torch.arange(nn)
             for m0 in range(0, S.shape[0], 16):       # m[img, src, dst], in chunks
                 img = torch.arange(m0, min(m0 + 16, S.shape[0]))
@@ -1685,9 +1745,15 @@ class DDStore:
                 v = vectors(*(x.reshape(-1) for x in g))
                 d2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
                 m.append((d2 <= r2).view(img.numel(), nn, nn))
+                dist.append(d2.view(img.numel(), nn, nn))
             m = torch.cat(m)
             if not loop:
                 m[zero].fill_diagonal_(False)
+            if k:  # per dst, over (image, src) in run order
+                m = self._thin_nearest(
+                    m.permute(2, 0, 1).reshape(nn, S.shape[0] * nn),
+                    torch.cat(dist).permute(2, 0, 1).reshape(nn, S.shape[0] * nn),
+                    k).view(nn, S.shape[0], nn).permute(1, 2, 0)
             dst, img, src = m.permute(2, 0, 1).nonzero(as_tuple=True)  # dst, shift, src
             edge_ptr[s + 1] = dst.numel()
             pairs.append(torch.stack([src, dst], 1) + ptr[s])
