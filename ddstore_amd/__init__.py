@@ -8,7 +8,7 @@ path. See ddstore_amd/csrc for the native core.
 """
 from .comm import Comm, as_comm
 from .store import (ColumnStats, DDStore, GraphBatch, PeriodicGraphBatch,
-                    RadiusGraphBatch)
+                    RadiusGraphBatch, TripletIndex)
 from .distdataset import DistDataset, nsplit
 from .prefetch import GraphPrefetchLoader, PrefetchLoader
 from .reshuffle import reshuffle_epoch
@@ -23,6 +23,7 @@ __all__ = [
     "GraphBatch",
     "RadiusGraphBatch",
     "PeriodicGraphBatch",
+    "TripletIndex",
     "ColumnStats",
     "DistDataset",
     "nsplit",

@@ -1188,6 +1188,74 @@ public:
         return {ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed};
     }
 
+    // Triplet index of a radius-graph batch (ddstore_kernels.h, triplet_count /
+    // triplet_fill), on stream() behind the fetch that wrote the batch.
+    // edge_index is the (2, Ecap) view of that fetch, int64 or int32;
+    // edge_shift its (Ecap, 3) int32 shifts, or an empty tensor for a batch
+    // without images; ptr / edge_ptr its offsets; ncap its node capacity.
+    // trip_out holds 2 * Tcap ids of edge_index's dtype; with size_trips it is
+    // allocated here, of exactly the counted triplets (trip_out only gives
+    // the dtype): the ONE path that reads device data on the host, trip_ptr[n]
+    // between count and fill. Returns (trip_out, trip_ptr); every element of
+    // trip_out is written, trip_ptr is [n+1] and never clamped.
+    std::tuple<at::Tensor, at::Tensor> build_triplets(
+        const at::Tensor& edge_index, const at::Tensor& edge_shift, const at::Tensor& ptr,
+        const at::Tensor& edge_ptr, int64_t ncap, at::Tensor trip_out, bool size_trips,
+        int64_t trip_fill) {
+        RoctxRange rr_("ddstore::build_triplets");
+        const char* op = "ddstore build_triplets: ";
+        auto here = [&](const at::Tensor& t) {
+            return t.is_contiguous() && t.device().is_cuda() &&
+                   t.device().index() == device_;
+        };
+        TORCH_CHECK((edge_index.scalar_type() == at::kLong ||
+                     edge_index.scalar_type() == at::kInt) &&
+                        edge_index.dim() == 2 && edge_index.size(0) == 2 &&
+                        here(edge_index),
+                    op, "edge_index must be a contiguous (2, Ecap) int64 or int32 "
+                        "tensor on the store device");
+        const int id_t = dds_type_of(edge_index);
+        const int64_t ecap = edge_index.size(1);
+        TORCH_CHECK(id_t == DDS_I64 || ecap < (int64_t(1) << 31), op,
+                    "int32 edge columns need Ecap < 2^31");
+        const bool shifts = edge_shift.numel() > 0;
+        TORCH_CHECK(!shifts || (edge_shift.scalar_type() == at::kInt && here(edge_shift) &&
+                                edge_shift.numel() == 3 * ecap),
+                    op, "edge_shift must be a contiguous int32 tensor of 3 * Ecap "
+                        "elements on the store device");
+        check_idx(ptr);
+        check_idx(edge_ptr);
+        TORCH_CHECK(ptr.numel() >= 1 && ptr.numel() == edge_ptr.numel() && ncap >= 0, op,
+                    "ptr and edge_ptr hold n + 1 offsets each");
+        TORCH_CHECK(trip_out.scalar_type() == edge_index.scalar_type(), op,
+                    "trip_out has the dtype of edge_index");
+        const int64_t nidx = ptr.numel() - 1;
+        auto opts = at::TensorOptions().dtype(at::kLong).device(ptr.device());
+        at::Tensor trip_ptr = at::empty({nidx + 1}, opts);
+        at::Tensor scratch = at::empty(
+            {(int64_t)ddstore::triplet_scratch_bytes(nidx, ncap, ecap)},
+            opts.dtype(at::kByte));
+        ddstore::triplet_count(stream(), edge_index.data_ptr(), id_t,
+                               shifts ? edge_shift.data_ptr<int32_t>() : nullptr,
+                               ptr.data_ptr<int64_t>(), edge_ptr.data_ptr<int64_t>(), nidx,
+                               ncap, ecap, scratch.data_ptr(),
+                               trip_ptr.data_ptr<int64_t>());
+        if (size_trips) {
+            const int64_t total = trip_ptr[nidx].item<int64_t>();  // syncs
+            trip_out = at::empty({2 * total}, trip_out.options());
+        }
+        TORCH_CHECK(here(trip_out) && trip_out.numel() % 2 == 0 &&
+                        (uintptr_t)trip_out.data_ptr() % dds_itemsize(id_t) == 0,
+                    op, "trip_out must be a contiguous tensor of 2 * Tcap ids on the "
+                        "store device");
+        const int64_t tcap = trip_out.numel() / 2;
+        ddstore::triplet_fill(stream(), ptr.data_ptr<int64_t>(),
+                              edge_ptr.data_ptr<int64_t>(), trip_ptr.data_ptr<int64_t>(),
+                              nidx, ncap, ecap, tcap, scratch.data_ptr(), id_t, trip_fill,
+                              trip_out.data_ptr());
+        return {trip_out, trip_ptr};
+    }
+
     // Padded CSR fetch: one launch writes the dense (n, max_len, disp)
     // batch (cast / affine fused, pad broadcast from `pad_bits`, the raw
     // bits of one output element) and the true per-sample lengths. The

@@ -34,6 +34,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.attr("MAX_PARTS") = DDS_MAX_PARTS;
     m.attr("RADIUS_TILE") = ddstore::radius_tile_nodes();
     m.attr("RADIUS_NEAREST_MAX") = ddstore::radius_nearest_max();
+    m.attr("TRIPLET_SLICE") = ddstore::triplet_slice();
     m.def("cycle_order", &ddstore::cycle_order,
           py::call_guard<py::gil_scoped_release>(),
           "Concatenated-cycle traversal of a permutation (order, starts)");
@@ -85,6 +86,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("gather_radius_graph", &DeviceStore::gather_radius_graph,
              py::call_guard<py::gil_scoped_release>())
         .def("gather_radius_graph_pbc", &DeviceStore::gather_radius_graph_pbc,
+             py::call_guard<py::gil_scoped_release>())
+        .def("build_triplets", &DeviceStore::build_triplets,
              py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_padded", &DeviceStore::gather_csr_padded,
              py::arg("name"), py::arg("idx"), py::arg("out"), py::arg("lengths"),

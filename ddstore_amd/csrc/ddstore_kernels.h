@@ -337,6 +337,48 @@ void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
                      const void* d_scratch, int out_t, bool coo, void* d_edge_out,
                      int32_t* d_shift_out, float* d_vec_out, bool nearest = false);
 
+// Triplet index of a radius-graph batch (DeviceStore::build_triplets). The
+// input is what radius_fill / radius_pbc_fill and graph_fill have written on
+// the same stream: d_edge_index the (2, ecap) ids of id_t (DDS_I64 or DDS_I32;
+// anything else launches nothing), d_shift the (ecap, 3) int32 image shifts or
+// nullptr (all zero), d_ptr / d_edge_ptr the [nidx+1] offsets. It is trusted
+// as their output -- a graph's edges ordered by dst, then shift, then src,
+// ids shifted by d_ptr[s] -- and not validated; ids out of range and unordered
+// runs give wrong triplets, never an access outside the arrays.
+//
+// Rule (docs/API.md, "Triplets"): graph s is kept iff d_ptr[s+1] <= ncap and
+// d_edge_ptr[s+1] <= ecap. A kept edge e = (j -> i, shift s_e) forms the
+// triplet (e', e) with every column e' of its graph whose dst is j, except the
+// one with src == i and shift == -s_e; triplets are ordered by e, then e'.
+//
+// triplet_count: d_trip_ptr[0..nidx] = exclusive scan of the per-graph triplet
+// counts, 0 for a graph that is not kept, never clamped by any capacity; the
+// per-edge offsets, run starts and excluded columns stay in d_scratch. Four
+// launches (three without edges). d_scratch: triplet_scratch_bytes(nidx, ncap,
+// ecap) bytes, no zeroing needed, independent of the number of triplets.
+//
+// triplet_fill: every element of the (2, tcap) output d_out of id_t. Row 0 is
+// e', row 1 is e, for the triplets of every kept graph with d_trip_ptr[s+1] <=
+// tcap, at columns d_trip_ptr[s] onwards; every other slot = trip_fill. 16-B
+// stores when tcap % 4 == 0 and d_out is 16-B aligned, element stores
+// otherwise. d_scratch and the other arguments are triplet_count's, on the
+// same stream. One launch; no atomics, no counters, no waiting between
+// workgroups in either.
+//
+// triplet_slice: the edges whose offsets one tile of the fill stages in LDS; a
+// tile that spans more (edges without triplets) searches them in global memory
+// (a second code path, for tests to aim at).
+int triplet_slice();
+size_t triplet_scratch_bytes(int64_t nidx, int64_t ncap, int64_t ecap);
+void triplet_count(hipStream_t stream, const void* d_edge_index, int id_t,
+                   const int32_t* d_shift, const int64_t* d_ptr,
+                   const int64_t* d_edge_ptr, int64_t nidx, int64_t ncap, int64_t ecap,
+                   void* d_scratch, int64_t* d_trip_ptr);
+void triplet_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_ptr,
+                  const int64_t* d_trip_ptr, int64_t nidx, int64_t ncap, int64_t ecap,
+                  int64_t tcap, const void* d_scratch, int id_t, int64_t trip_fill,
+                  void* d_out);
+
 // MX (OCP microscaling v1.0) block-scaled storage. A variable of logical
 // width `disp` keeps each row packed as
 //   [nblk * 32 element codes][nblk E8M0 scale bytes][zero pad to 16 B]

@@ -1243,8 +1243,9 @@ __device__ __forceinline__ void fill_store16(T* __restrict__ dst, int64_t n, T v
     for (int64_t i = h + nb * V + tid; i < n; i += nthreads) dst[i] = val;
 }
 
-// Largest k in [0, n] with a[k] <= cap, for a monotone a[0..n] with a[0] = 0
-// and cap >= 0, found by the whole block: every round samples the candidate
+// Largest k in [0, n] with a[k] <= cap, for a monotone a[0..n] with a[0] <=
+// cap (offsets: a[0] = 0, cap >= 0; the triplet fill also starts it inside an
+// array), found by the whole block: every round samples the candidate
 // range at kBlock points and keeps the one stride that holds the answer
 // (three rounds for 2^24 entries, one load per thread and round). Returns
 // the same k in every thread.
@@ -2589,6 +2590,306 @@ const GatherKnobs& gather_knobs() {
     return k;
 }
 
+// ---------------------------------------------------------------------------
+// Triplet index (DeviceStore::build_triplets): for every kept edge e = (j ->
+// i) of a radius-graph batch the edges e' = (k -> j), without the one way
+// straight back to i through the same image. Both fetches order a graph's
+// edges by dst, then shift, then src, and shift ids by ptr[g], so over the
+// kept edges the dst row is non-decreasing: the edges into a node are one
+// contiguous sorted run, and the excluded edge is found in it by a binary
+// search on (-s_e, i). Index construction, no MFMA. Five launches:
+//   k_triplet_runs    node_start[v] = first column with dst >= v
+//   k_triplet_count   per edge: its run's start, the excluded column and the
+//                     triplet offset inside its graph; per graph: the total
+//   k_radius_scan     trip_ptr, reused as it is
+//   k_triplet_rebase  offsets made absolute (+ trip_ptr[g]), one sentinel
+//                     entry behind the last kept edge
+//   k_triplet_fill    both rows of the output, balanced by output
+// The first two and the fourth are O(nodes + edges). The triplets outnumber
+// the edges about tenfold, so the cost sits in the fill: a workgroup owns
+// kTripletTile consecutive slots and a block a run of consecutive tiles. The
+// first edge of a block's first tile comes from a block-wide search over the
+// absolute offsets (block_last_le, a load per thread and round, not a
+// dependent chain), that of every later tile from one round over the kBlock
+// entries behind the tile before. The block stages the window of offsets
+// behind that edge in LDS, then run starts and excluded columns of the edges
+// the tile really covers (24 B per edge), and every lane builds 4
+// consecutive slots for 16-B stores into both rows: row 1 repeats the edge's
+// column, row 0 counts up from the run's start and steps over the excluded
+// column. An edge without triplets (a dimer's) takes no slot, so a tile's
+// span of edges is unbounded; a span past the slice searches the same arrays
+// in global memory. Slots behind the written prefix get the fill value in the
+// same launch. No kernel waits on another workgroup and no atomics; every
+// search runs over a range clamped to its arrays, and the offsets are
+// non-decreasing by construction (every count is >= 0) whatever the ids are.
+// ---------------------------------------------------------------------------
+
+constexpr int kTripletPer = 4;                      // slots per lane
+constexpr int kTripletTile = kBlock * kTripletPer;  // slots per workgroup
+constexpr int kTripletSlice = 512;                  // edges staged in LDS
+
+__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t lo, int64_t hi) {
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// The graphs whose edges are in the batch: the prefix with ptr[k] <= ncap and
+// edge_ptr[k] <= ecap. Block-uniform; every thread of the block calls it.
+__device__ __forceinline__ int64_t triplet_kept(const int64_t* __restrict__ ptr,
+                                                const int64_t* __restrict__ edge_ptr,
+                                                int64_t nidx, int64_t ncap,
+                                                int64_t ecap) {
+    const int64_t kn = block_last_le(ptr, nidx, ncap);
+    const int64_t ke = block_last_le(edge_ptr, nidx, ecap);
+    return kn < ke ? kn : ke;
+}
+
+// node_start[v] = first kept column e with dst[e] >= v, for v in [0, kept
+// nodes]: thread e fills the gap (dst[e-1], dst[e]], the thread behind the
+// last edge the rest. O(nodes + edges), no search.
+template <typename Tid>
+__global__ void __launch_bounds__(kBlock)
+k_triplet_runs(const Tid* __restrict__ dst, const int64_t* __restrict__ ptr,
+               const int64_t* __restrict__ edge_ptr, int64_t nidx, int64_t ncap,
+               int64_t ecap, int64_t* __restrict__ node_start) {
+    const int64_t kk = triplet_kept(ptr, edge_ptr, nidx, ncap, ecap);
+    const int64_t nodes = clamp_i64(ptr[kk], 0, ncap);
+    const int64_t edges = clamp_i64(edge_ptr[kk], 0, ecap);
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e <= edges;
+         e += (int64_t)gridDim.x * kBlock) {
+        int64_t lo = e == 0 ? 0 : (int64_t)dst[e - 1] + 1;
+        int64_t hi = e == edges ? nodes : (int64_t)dst[e];
+        if (lo < 0) lo = 0;
+        if (hi > nodes) hi = nodes;
+        for (int64_t v = lo; v <= hi; ++v) node_start[v] = e;
+    }
+}
+
+// Per kept edge e = (j -> i): run0[e] = first column of R(j), skip[e] = the
+// column of the edge (i -> j) with the negated shift, or -1, and off[e] = the
+// triplets of the graph's edges in front of e. counts[s] = the graph's total,
+// 0 for a graph that is not kept. GROUP lanes stream a graph's edges, GROUP
+// at a time, a group scan with a running carry between the rounds.
+template <typename Tid, bool SHIFT, int GROUP>
+__global__ void __launch_bounds__(kBlock)
+k_triplet_count(const Tid* __restrict__ ei, const int32_t* __restrict__ shift,
+                const int64_t* __restrict__ ptr, const int64_t* __restrict__ edge_ptr,
+                int64_t nidx, int64_t ncap, int64_t ecap,
+                const int64_t* __restrict__ node_start, int64_t* __restrict__ counts,
+                int64_t* __restrict__ off, int64_t* __restrict__ run0,
+                int64_t* __restrict__ skip) {
+    constexpr int GPB = kBlock / GROUP;
+    const Tid* __restrict__ src = ei;
+    const Tid* __restrict__ dst = ei + ecap;
+    const int tid = threadIdx.x % GROUP;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        const int64_t e0 = edge_ptr[s], e1 = edge_ptr[s + 1];
+        int64_t carry = 0;
+        if (p0 >= 0 && p1 >= p0 && p1 <= ncap && e0 >= 0 && e1 > e0 && e1 <= ecap) {
+            for (int64_t base = e0; base < e1; base += GROUP) {  // group-uniform
+                const int64_t e = base + tid;
+                int64_t cnt = 0;
+                if (e < e1) {
+                    const int64_t j = (int64_t)src[e], i = (int64_t)dst[e];
+                    int64_t a = e0, b = e0;
+                    if (j >= p0 && j < p1) {
+                        a = clamp_i64(node_start[j], e0, e1);
+                        b = clamp_i64(node_start[j + 1], a, e1);
+                    }
+                    int64_t k0 = 0, k1 = 0, k2 = 0;
+                    if constexpr (SHIFT) {
+                        k0 = -(int64_t)shift[3 * e];
+                        k1 = -(int64_t)shift[3 * e + 1];
+                        k2 = -(int64_t)shift[3 * e + 2];
+                    }
+                    // first column of the run whose (shift, src) is not below
+                    // the key (-s_e, i), in the run's own order
+                    int64_t lo = a, hi = b;
+                    while (lo < hi) {
+                        const int64_t mid = lo + ((hi - lo) >> 1);
+                        bool below;
+                        if constexpr (SHIFT) {
+                            const int64_t m0 = shift[3 * mid], m1 = shift[3 * mid + 1];
+                            const int64_t m2 = shift[3 * mid + 2];
+                            below = m0 != k0 ? m0 < k0
+                                  : m1 != k1 ? m1 < k1
+                                  : m2 != k2 ? m2 < k2 : (int64_t)src[mid] < i;
+                        } else {
+                            below = (int64_t)src[mid] < i;
+                        }
+                        if (below) lo = mid + 1; else hi = mid;
+                    }
+                    bool found = lo < b && (int64_t)src[lo] == i;
+                    if constexpr (SHIFT)
+                        found = found && shift[3 * lo] == k0 && shift[3 * lo + 1] == k1 &&
+                                shift[3 * lo + 2] == k2;
+                    run0[e] = a;
+                    skip[e] = found ? lo : -1;
+                    cnt = (b - a) - (found ? 1 : 0);
+                }
+                int64_t incl = cnt;
+                for (int o = 1; o < GROUP; o <<= 1) {
+                    const int64_t up = __shfl_up(incl, o, GROUP);
+                    if (tid >= o) incl += up;
+                }
+                if (e < e1) off[e] = carry + (incl - cnt);
+                carry += __shfl(incl, GROUP - 1, GROUP);
+            }
+        }
+        if (tid == 0) counts[s] = carry;
+    }
+}
+
+// off[e] += trip_ptr[s] for the edges of every kept graph s, and behind the
+// last kept graph's edges one entry more, the kept total: off[0 .. kept
+// edges] is then the non-decreasing array the fill searches.
+template <int GROUP>
+__global__ void __launch_bounds__(kBlock)
+k_triplet_rebase(const int64_t* __restrict__ ptr, const int64_t* __restrict__ edge_ptr,
+                 const int64_t* __restrict__ trip_ptr, int64_t nidx, int64_t ncap,
+                 int64_t ecap, int64_t* __restrict__ off) {
+    constexpr int GPB = kBlock / GROUP;
+    const int tid = threadIdx.x % GROUP;
+    for (int64_t s = (int64_t)blockIdx.x * GPB + threadIdx.x / GROUP; s < nidx;
+         s += (int64_t)gridDim.x * GPB) {
+        const int64_t e0 = edge_ptr[s], e1 = edge_ptr[s + 1];
+        if (ptr[s] < 0 || ptr[s + 1] > ncap || e0 < 0 || e1 < e0 || e1 > ecap) continue;
+        const int64_t base = trip_ptr[s];
+        for (int64_t e = e0 + tid; e < e1; e += GROUP) off[e] += base;
+        const bool last = s + 1 == nidx || ptr[s + 2] > ncap || edge_ptr[s + 2] > ecap;
+        if (last && tid == 0) off[e1] = trip_ptr[s + 1];
+    }
+}
+
+// Both rows of the (2, tcap) output. With kt the graphs whose triplets are
+// written (the kept ones with trip_ptr[k] <= tcap) slot t < trip_ptr[kt]
+// belongs to the edge e with off[e] <= t < off[e+1]: row 1 = e, row 0 =
+// run0[e] + r + (that column >= skip[e]) with r = t - off[e]. Every other slot
+// = fill. VEC: 16-B stores (tcap % 4 == 0 and a 16-B aligned output).
+template <typename Tid, bool VEC>
+__global__ void __launch_bounds__(kBlock)
+k_triplet_fill(const int64_t* __restrict__ ptr, const int64_t* __restrict__ edge_ptr,
+               const int64_t* __restrict__ trip_ptr, int64_t nidx, int64_t ncap,
+               int64_t ecap, int64_t tcap, const int64_t* __restrict__ off,
+               const int64_t* __restrict__ run0, const int64_t* __restrict__ skip,
+               Tid fill, Tid* __restrict__ out) {
+    __shared__ int64_t s_off[kTripletSlice + 1];
+    __shared__ int64_t s_run[kTripletSlice];
+    __shared__ int64_t s_skip[kTripletSlice];
+    const int64_t kk = triplet_kept(ptr, edge_ptr, nidx, ncap, ecap);
+    const int64_t kt = block_last_le(trip_ptr, kk, tcap);
+    const int64_t tend = clamp_i64(trip_ptr[kt], 0, tcap);
+    const int64_t eend = clamp_i64(edge_ptr[kt], 0, ecap);
+    const int64_t ntiles = (tcap + kTripletTile - 1) / kTripletTile;
+    // consecutive tiles per block: the first edge of a tile is found from the
+    // first edge of the tile before it
+    const int64_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+    const int64_t tile_lo = (int64_t)blockIdx.x * per;
+    const int64_t tile_hi = tile_lo + per < ntiles ? tile_lo + per : ntiles;
+    int64_t ea = -1;  // last edge with off <= t0 of the tile before
+    for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+        const int64_t t0 = tile * kTripletTile;
+        const int64_t s = t0 + (int64_t)threadIdx.x * kTripletPer;
+        Tid r0[kTripletPer], r1[kTripletPer];
+#pragma unroll
+        for (int k = 0; k < kTripletPer; ++k) r0[k] = r1[k] = fill;
+        if (t0 < tend && eend > 0) {  // block-uniform
+            const int64_t tl = t0 + kTripletTile < tend ? t0 + kTripletTile : tend;
+            // ea = last edge with off <= t0 (< eend, as t0 < off[eend]): the
+            // whole array once, then the kBlock entries from the old ea in
+            // one round, and the rest of the array only behind those
+            if (ea < 0) {
+                ea = block_last_le(off, eend, t0);
+            } else {
+                const int64_t q = ea + threadIdx.x;
+                const int c = __syncthreads_count(q <= eend && off[q] <= t0);  // >= 1
+                if (c < kBlock)
+                    ea += c > 0 ? c - 1 : 0;
+                else
+                    ea += kBlock - 1 + block_last_le(off + ea + kBlock - 1,
+                                                     eend - ea - (kBlock - 1), t0);
+            }
+            // the window of offsets behind ea; it covers the tile iff its last
+            // entry is past the tile's last slot (always, if it ends at eend)
+            const int64_t win = eend - ea < kTripletSlice ? eend - ea : kTripletSlice;
+            // (the block-wide round of the ea step stands between the reads of
+            // the tile before and these writes)
+            for (int64_t m = threadIdx.x; m <= win; m += kBlock) s_off[m] = off[ea + m];
+            __syncthreads();
+            const bool staged = s_off[win] > tl - 1;
+            int64_t span;  // edges ea .. ea + span - 1 hold the tile's slots
+            if (staged) {
+                int64_t lo = 0, hi = win - 1;  // uniform: LDS broadcasts
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi + 1) >> 1;
+                    if (s_off[mid] <= tl - 1) lo = mid; else hi = mid - 1;
+                }
+                span = lo + 1;
+                for (int64_t m = threadIdx.x; m < span; m += kBlock) {
+                    s_run[m] = run0[ea + m];
+                    s_skip[m] = skip[ea + m];
+                }
+                __syncthreads();
+            } else {  // off[ea + win] <= tl - 1: the last edge is behind the window
+                span = win + 1 + block_last_le(off + ea + win, eend - ea - win, tl - 1);
+            }
+            auto build = [&](const int64_t* po, const int64_t* pr, const int64_t* pk) {
+                int64_t at = -1, cur = 0, nxt = 0, a = 0, sk = -1;
+#pragma unroll
+                for (int k = 0; k < kTripletPer; ++k) {
+                    const int64_t t = s + k;
+                    if (t >= tl) break;
+                    if (at < 0 || t >= nxt) {  // last edge of the span with po <= t
+                        int64_t lo = at + 1 < span ? at + 1 : span - 1, hi = span - 1;
+                        while (lo < hi) {
+                            const int64_t mid = (lo + hi + 1) >> 1;
+                            if (po[mid] <= t) lo = mid; else hi = mid - 1;
+                        }
+                        at = lo;
+                        cur = po[at];
+                        nxt = po[at + 1];
+                        a = pr[at];
+                        sk = pk[at];
+                    }
+                    int64_t c = a + (t - cur);
+                    if (sk >= 0 && c >= sk) ++c;
+                    r0[k] = static_cast<Tid>(c);
+                    r1[k] = static_cast<Tid>(ea + at);
+                }
+            };
+            if (s < tl) {
+                if (staged) build(s_off, s_run, s_skip);
+                else build(off + ea, run0 + ea, skip + ea);
+            }
+        }
+        if (s >= tcap) continue;
+        if constexpr (VEC) {
+            constexpr int V = 16 / (int)sizeof(Tid);
+            using Vt = VecT<Tid, V>;
+#pragma unroll
+            for (int h = 0; h < kTripletPer / V; ++h) {
+                Vt v0, v1;
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    v0.v[k] = r0[h * V + k];
+                    v1.v[k] = r1[h * V + k];
+                }
+                *reinterpret_cast<Vt*>(out + s + h * V) = v0;
+                *reinterpret_cast<Vt*>(out + tcap + s + h * V) = v1;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kTripletPer; ++k) {
+                if (s + k < tcap) {
+                    out[s + k] = r0[k];
+                    out[tcap + s + k] = r1[k];
+                }
+            }
+        }
+    }
+}
+
 // CU count of the device the store runs on (one device per process),
 // queried once.
 int cu_count() {
@@ -3355,6 +3656,87 @@ void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
         if (pos_t == DDS_F64) launch_out(TypeTag<double>{}, G);
         else if (pos_t == DDS_F32) launch_out(TypeTag<float>{}, G);
     });
+}
+
+int triplet_slice() { return kTripletSlice; }
+
+// Scratch of the triplet builder: counts, node_start, off (one entry behind
+// the last edge), run0, skip -- int64 each.
+size_t triplet_scratch_bytes(int64_t nidx, int64_t ncap, int64_t ecap) {
+    return (size_t)((nidx + 1) + (ncap + 1) + (ecap + 1) + 2 * ecap) * 8;
+}
+
+void triplet_count(hipStream_t stream, const void* d_edge_index, int id_t,
+                   const int32_t* d_shift, const int64_t* d_ptr,
+                   const int64_t* d_edge_ptr, int64_t nidx, int64_t ncap, int64_t ecap,
+                   void* d_scratch, int64_t* d_trip_ptr) {
+    if (id_t != DDS_I64 && id_t != DDS_I32) return;
+    int64_t* counts = reinterpret_cast<int64_t*>(d_scratch);
+    int64_t* node_start = counts + nidx + 1;
+    int64_t* off = node_start + ncap + 1;
+    int64_t* run0 = off + ecap + 1;
+    int64_t* skip = run0 + ecap;
+    const int group = radius_group(nidx, ncap);
+    const int64_t by_graph = (nidx + (kBlock / group) - 1) / (kBlock / group);
+    const int64_t cap = (int64_t)cu_count() * kBlocksPerCU;
+    const int grid = (int)(by_graph < 1 ? 1 : (by_graph < cap ? by_graph : cap));
+    auto launch = [&](auto ti) {
+        using Tid = typename decltype(ti)::type;
+        const Tid* ei = (const Tid*)d_edge_index;
+        if (nidx > 0 && ecap > 0) {
+            hipLaunchKernelGGL((k_triplet_runs<Tid>), dim3(n_blocks(ecap + 1)),
+                               dim3(kBlock), 0, stream, ei + ecap, d_ptr, d_edge_ptr, nidx,
+                               ncap, ecap, node_start);
+        }
+        if (nidx > 0) {
+            dispatch_group<16, 64>(group, [&](auto G) {
+                auto go = [&](auto kern) {
+                    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, stream, ei,
+                                       d_shift, d_ptr, d_edge_ptr, nidx, ncap, ecap,
+                                       (const int64_t*)node_start, counts, off, run0, skip);
+                };
+                if (d_shift) go(k_triplet_count<Tid, true, G()>);
+                else go(k_triplet_count<Tid, false, G()>);
+            });
+        }
+    };
+    if (id_t == DDS_I64) launch(TypeTag<int64_t>{});
+    else launch(TypeTag<int32_t>{});
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, counts, nidx,
+                       d_trip_ptr);
+    if (nidx > 0)
+        dispatch_group<16, 64>(group, [&](auto G) {
+            hipLaunchKernelGGL((k_triplet_rebase<G()>), dim3(grid), dim3(kBlock), 0, stream,
+                               d_ptr, d_edge_ptr, (const int64_t*)d_trip_ptr, nidx, ncap,
+                               ecap, off);
+        });
+}
+
+void triplet_fill(hipStream_t stream, const int64_t* d_ptr, const int64_t* d_edge_ptr,
+                  const int64_t* d_trip_ptr, int64_t nidx, int64_t ncap, int64_t ecap,
+                  int64_t tcap, const void* d_scratch, int id_t, int64_t trip_fill,
+                  void* d_out) {
+    if (tcap <= 0 || (id_t != DDS_I64 && id_t != DDS_I32)) return;
+    const int64_t* off = reinterpret_cast<const int64_t*>(d_scratch) + (nidx + 1) +
+                         (ncap + 1);
+    const int64_t* run0 = off + ecap + 1;
+    const int64_t* skip = run0 + ecap;
+    const int64_t ntiles = (tcap + kTripletTile - 1) / kTripletTile;
+    const int64_t cap = (int64_t)cu_count() * kBlocksPerCU;
+    const int grid = (int)(ntiles < cap ? ntiles : cap);
+    const bool vec = tcap % kTripletPer == 0 && (uintptr_t)d_out % 16 == 0;
+    auto launch = [&](auto ti) {
+        using Tid = typename decltype(ti)::type;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, stream, d_ptr,
+                               d_edge_ptr, d_trip_ptr, nidx, ncap, ecap, tcap, off, run0,
+                               skip, (Tid)trip_fill, (Tid*)d_out);
+        };
+        if (vec) go(k_triplet_fill<Tid, true>);
+        else go(k_triplet_fill<Tid, false>);
+    };
+    if (id_t == DDS_I64) launch(TypeTag<int64_t>{});
+    else launch(TypeTag<int32_t>{});
 }
 
 void scatter_rows_local(hipStream_t stream,

@@ -96,6 +96,14 @@ class PeriodicGraphBatch(NamedTuple):
     node_extras: tuple         # ((values, offsets), ...)
 
 
+class TripletIndex(NamedTuple):
+    """The angle index of a radius-graph batch, as :meth:`DDStore.get_triplets`
+    returns it: for every edge ``j -> i`` the edges ``k -> j``."""
+
+    triplets: torch.Tensor     # (2, Tcap) edge columns: row 0 idx_kj, row 1 idx_ji
+    trip_ptr: torch.Tensor     # int64 (n+1,) triplet offsets, never clamped
+
+
 class ColumnStats(NamedTuple):
     """Per-column statistics of a variable, as :meth:`DDStore.column_stats`
     returns them. Column ``c`` is flat position ``c`` of a row (CSR: of an
@@ -1785,6 +1793,129 @@ class DDStore:
             if edge_vec:
                 vec_out.view(ecap, 3)[:edge_end] = torch.cat(vecs)[:edge_end]
         return ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed
+
+    # ----------------------------------------------------------------- triplets
+    def get_triplets(self, batch, *, trip_out: Optional[torch.Tensor] = None,
+                     trip_fill: int = -1) -> TripletIndex:
+        """The triplet index ``k -> j -> i`` of a radius-graph batch, for
+        angle-based models (DimeNet, GemNet): for every edge ``j -> i`` the
+        edges ``k -> j`` that form an angle with it. Built natively on the GPU
+        from the edge list the fetch has just written; with ``trip_out`` the
+        call makes no host sync. It runs on the store's stream behind the
+        fetch that produced ``batch``.
+
+        ``batch`` is a :class:`RadiusGraphBatch` or a
+        :class:`PeriodicGraphBatch` of a ``coo=True`` call on this store; a
+        :class:`GraphBatch`, whose stored edges promise no order, is a
+        ``TypeError``, an ``edge_index`` with ``shape[0] != 2`` a
+        ``ValueError``. The batch is trusted as the output of those fetches
+        (a graph's edges ordered by ``dst``, then shift, then ``src``): ids
+        and order are not validated.
+
+        The rule is all integers and the same on both backends. With ``n =
+        len(batch.ptr) - 1`` and the capacities ``Ncap``, ``Ecap`` of the
+        batch, graph ``g`` is *kept* iff its edges were written: ``ptr[g+1] <=
+        Ncap`` and ``edge_ptr[g+1] <= Ecap``. For a kept edge at column ``e``
+        let ``j = edge_index[0, e]``, ``i = edge_index[1, e]``, ``s_e =
+        edge_shift[e]`` (zero for a :class:`RadiusGraphBatch`) and ``R(j)``
+        the columns ``e'`` of the same graph with ``edge_index[1, e'] == j``.
+        Edge ``e`` forms the triplet ``(idx_kj = e', idx_ji = e)`` with every
+        ``e'`` in ``R(j)`` except the one with ``edge_index[0, e'] == i`` and
+        ``s_e' + s_e == 0`` in all three components: the same atom ``i``,
+        reached back through the same image. There is at most one such edge;
+        under a neighbour cap there may be none; with ``loop=True`` a
+        self-loop excludes itself. With all shifts zero this is PyG's ``idx_i
+        != idx_k``, with shifts OCP's ``(idx_i != idx_k) | any(offset_kj +
+        offset_ji != 0)``. Triplets are ordered by ``e``, then ``e'``, the
+        order PyG's construction gives for this edge list.
+
+        * ``trip_ptr`` int64 ``(n+1,)``: the exclusive scan of the graphs'
+          triplet counts; a graph that is not kept counts 0; never clamped by
+          ``Tcap``, so ``trip_ptr[-1] > Tcap`` tells that graphs were cut;
+        * ``triplets`` ``(2, Tcap)`` in the dtype of ``edge_index``: row 0 is
+          ``idx_kj``, row 1 ``idx_ji``, both edge columns of the batch. A
+          graph's triplets are written iff it is kept and ``trip_ptr[g+1] <=
+          Tcap`` (a prefix); every other slot holds ``trip_fill``, converted
+          once to that dtype (a value it cannot hold: ``ValueError``). Every
+          element is written.
+
+        ``trip_out`` is a contiguous tensor of ``2 * Tcap`` elements of that
+        dtype on the store device (``ValueError`` otherwise). Without it the
+        call counts, reads ``trip_ptr[-1]`` back, allocates exactly that much
+        and fills: that path syncs with the device."""
+        what = "get_triplets"
+        if not isinstance(batch, (RadiusGraphBatch, PeriodicGraphBatch)):
+            raise TypeError(
+                f"ddstore {what}: batch must be a RadiusGraphBatch or a "
+                "PeriodicGraphBatch (stored edges have no run order)")
+        ei = batch.edge_index
+        if ei.dim() != 2 or ei.shape[0] != 2:
+            raise ValueError(f"ddstore {what}: edge_index must be (2, Ecap): fetch "
+                             "the batch with coo=True")
+        if (ei.dtype not in (torch.int32, torch.int64) or not ei.is_contiguous()
+                or ei.device != self.device):
+            raise ValueError(f"ddstore {what}: edge_index must be a contiguous int32 "
+                             "or int64 tensor on the store device")
+        if trip_out is not None and (
+                trip_out.dtype != ei.dtype or not trip_out.is_contiguous()
+                or trip_out.device != self.device or trip_out.numel() % 2):
+            raise ValueError(
+                f"ddstore {what}: trip_out must be a contiguous {ei.dtype} tensor of "
+                "2 * Tcap elements on the store device")
+        ecap, ncap = ei.shape[1], batch.batch.numel()
+        if ei.dtype == torch.int32 and ecap >= 2 ** 31:
+            raise ValueError(f"ddstore {what}: int32 edge columns need Ecap < 2**31")
+        shift = batch.edge_shift if isinstance(batch, PeriodicGraphBatch) else None
+        try:
+            fill = int(torch.tensor([trip_fill], dtype=ei.dtype).item())
+        except (RuntimeError, OverflowError, TypeError) as exc:
+            raise ValueError(
+                f"ddstore {what}: trip_fill must be representable in {ei.dtype}") from exc
+        sized = trip_out is None
+        if sized:
+            trip_out = torch.empty(0, dtype=ei.dtype, device=self.device)
+        if self.mode == "hip":
+            if shift is None:
+                shift = torch.empty(0, dtype=torch.int32, device=self.device)
+            trip_out, trip_ptr = self._backend.build_triplets(
+                ei, shift.contiguous(), batch.ptr, batch.edge_ptr, ncap, trip_out,
+                sized, fill)
+        else:
+            trip_out, trip_ptr = self._triplets_host(
+                ei, shift, batch.ptr, batch.edge_ptr, ncap, trip_out, sized, fill)
+        return TripletIndex(trip_out.view(2, trip_out.numel() // 2), trip_ptr)
+
+    @staticmethod
+    def _triplets_host(ei, shift, ptr, edge_ptr, ncap, trip_out, sized, fill):
+        """Host path of :meth:`get_triplets`, PyG's construction on the kept
+        edges: every edge paired with the whole run into its source, then the
+        way back masked out."""
+        n, ecap = ptr.numel() - 1, ei.shape[1]
+        kk = min(int((ptr[1:] <= ncap).sum()), int((edge_ptr[1:] <= ecap).sum()))
+        ee, nodes = int(edge_ptr[kk]), int(ptr[kk])
+        src, dst = ei[0, :ee].long(), ei[1, :ee].long()
+        # dst is non-decreasing over the kept edges: R(v) = [start[v], start[v+1])
+        start = torch.searchsorted(dst.contiguous(), torch.arange(nodes + 1))
+        a, deg = start[src], start[src + 1] - start[src]
+        ji = torch.repeat_interleave(torch.arange(ee), deg)
+        kj = a[ji] + (torch.arange(ji.numel()) - (torch.cumsum(deg, 0) - deg)[ji])
+        back = src[kj] == dst[ji]
+        if shift is not None:
+            s = shift.view(ecap, 3)[:ee].long()
+            back &= (s[kj] + s[ji] == 0).all(1)
+        ji, kj = ji[~back], kj[~back]
+        graph = torch.searchsorted(edge_ptr[1:kk + 1].contiguous(), ji, right=True)
+        trip_ptr = torch.zeros(n + 1, dtype=torch.int64)
+        torch.cumsum(torch.bincount(graph, minlength=n), 0, out=trip_ptr[1:])
+        if sized:
+            trip_out = torch.empty(2 * int(trip_ptr[-1]), dtype=ei.dtype)
+        tcap = trip_out.numel() // 2
+        tend = int(trip_ptr[int((trip_ptr[1:kk + 1] <= tcap).sum())])
+        out = trip_out.view(2, tcap)
+        out[:, tend:] = fill
+        out[0, :tend] = kj[:tend]
+        out[1, :tend] = ji[:tend]
+        return trip_out, trip_ptr
 
     def local_shard(self, name: str) -> torch.Tensor:
         """Zero-copy view of this rank's shard (rows x disp). Valid until
