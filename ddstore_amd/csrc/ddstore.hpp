@@ -964,12 +964,14 @@ public:
     // element of batch_out and edge_out is written; vec_out only on rows of
     // kept edges. With `nearest`, max_neighbors (1..radius_nearest_max()) keeps
     // every dst's nearest sources instead of its first ones: the select kernel
-    // stands for the count pass.
+    // stands for the count pass. With `cells` (not with `nearest`) the cell-list
+    // launchers radius_cells_count / radius_cells_fill stand for radius_count /
+    // radius_fill: the same outputs bit for bit.
     std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gather_radius_graph(
         const std::string& pos_name, const at::Tensor& idx, double r,
         int64_t max_neighbors, bool loop, at::Tensor pos_out, at::Tensor edge_out,
         at::Tensor batch_out, at::Tensor vec_out, bool edge_vec, bool size_edges,
-        bool coo, int64_t edge_fill, bool nearest) {
+        bool coo, int64_t edge_fill, bool nearest, bool cells) {
         RoctxRange rr_("ddstore::gather_radius_graph");
         DeviceVar& pv = var(pos_name);
         TORCH_CHECK(pv.is_csr, "ddstore gather_radius_graph: not a CSR variable");
@@ -987,8 +989,13 @@ public:
                                  max_neighbors <= ddstore::radius_nearest_max()),
                     "ddstore gather_radius_graph: the nearest cap is in 1..",
                     ddstore::radius_nearest_max());
+        TORCH_CHECK(!(cells && nearest),
+                    "ddstore gather_radius_graph: the cell-list path has no nearest cap");
         const int64_t nidx = idx.numel();
         const int64_t ncap = pos_out.numel() / 3;
+        TORCH_CHECK(!cells || ncap + nidx < (int64_t(1) << 31),
+                    "ddstore gather_radius_graph: the cell-list path needs "
+                    "Ncap + n < 2^31");
         TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
                         batch_out.device().is_cuda() &&
                         batch_out.device().index() == device_ &&
@@ -1006,9 +1013,16 @@ public:
         auto bopts = at::TensorOptions().dtype(at::kByte).device(idx.device());
         at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
         at::Tensor scratch = at::empty(
-            {(int64_t)ddstore::radius_scratch_bytes(nidx, ncap, nearest)}, bopts);
+            {(int64_t)(cells ? ddstore::radius_cells_scratch_bytes(nidx, ncap)
+                             : ddstore::radius_scratch_bytes(nidx, ncap, nearest))},
+            bopts);
         if (nidx == 0) {
             edge_ptr.zero_();
+        } else if (cells) {
+            ddstore::radius_cells_count(stream(), pos_out.data_ptr(), pv.dds_t,
+                                        ptr.data_ptr<int64_t>(), nidx, ncap, rf,
+                                        max_neighbors, loop, scratch.data_ptr(),
+                                        edge_ptr.data_ptr<int64_t>());
         } else if (nearest) {
             ddstore::radius_nearest_select(
                 stream(), pos_out.data_ptr(), pv.dds_t, ptr.data_ptr<int64_t>(), nidx,
@@ -1046,7 +1060,13 @@ public:
             // nothing is written through it
             d_vec = ecap ? vec_out.data_ptr<float>() : nullptr;
         }
-        if (nidx > 0)
+        if (nidx > 0 && cells)
+            ddstore::radius_cells_fill(stream(), pos_out.data_ptr(), pv.dds_t,
+                                       ptr.data_ptr<int64_t>(),
+                                       edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, rf,
+                                       loop, scratch.data_ptr(), out_t, coo,
+                                       edge_out.data_ptr(), d_vec);
+        else if (nidx > 0)
             ddstore::radius_fill(stream(), pos_out.data_ptr(), pv.dds_t,
                                  ptr.data_ptr<int64_t>(), edge_ptr.data_ptr<int64_t>(),
                                  nidx, ncap, ecap, r2, loop, scratch.data_ptr(), out_t,

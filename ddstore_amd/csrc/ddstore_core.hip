@@ -34,6 +34,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.attr("MAX_PARTS") = DDS_MAX_PARTS;
     m.attr("RADIUS_TILE") = ddstore::radius_tile_nodes();
     m.attr("RADIUS_NEAREST_MAX") = ddstore::radius_nearest_max();
+    m.attr("RADIUS_CELLS_SORT_MAX") = ddstore::radius_cells_sort_max();
+    m.attr("RADIUS_CELLS_MIN_NODES") = ddstore::radius_cells_min_nodes();
     m.attr("TRIPLET_SLICE") = ddstore::triplet_slice();
     m.def("cycle_order", &ddstore::cycle_order,
           py::call_guard<py::gil_scoped_release>(),

@@ -288,6 +288,38 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
                  const void* d_scratch, int out_t, bool coo, void* d_edge_out,
                  float* d_vec_out, bool nearest = false);
 
+// Cell-list path of the same fetch (docs/API.md, algorithm = "cells"): the
+// same rule, order and outputs bit for bit, found through a spatial grid per
+// graph in O(nodes), every graph spread over the whole device. The launchers
+// take r itself (the bin width comes from it; r2 = r * r in f32 as above).
+//
+// radius_cells_count stands for radius_count: d_edge_ptr as it leaves it, and
+// in d_scratch the nodes in bin order, the grids and every node's first edge
+// slot for radius_cells_fill. d_scratch: radius_cells_scratch_bytes(nidx,
+// ncap) bytes, under 112 * (ncap + nidx) + 256 whatever the coordinates are,
+// 16-byte aligned, no zeroing needed. Needs ncap + nidx < 2^31, which the
+// caller checks. Integer atomics place the nodes in their bins; the outputs
+// do not depend on their order. No floating-point atomics.
+//
+// radius_cells_fill stands for radius_fill (no nearest mode): the same slots
+// written and the same left alone. One launch.
+//
+// radius_cells_sort_max: the kept edges of one dst that are ordered in LDS; a
+// dst with more takes a slower exact path (for tests to aim at).
+// radius_cells_min_nodes: the largest-sample size from which the store's
+// "auto" takes this path.
+int radius_cells_sort_max();
+int radius_cells_min_nodes();
+size_t radius_cells_scratch_bytes(int64_t nidx, int64_t ncap);
+void radius_cells_count(hipStream_t stream, const void* d_pos, int pos_t,
+                        const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r,
+                        int64_t max_neighbors, bool loop, void* d_scratch,
+                        int64_t* d_edge_ptr);
+void radius_cells_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                       const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                       int64_t ncap, int64_t ecap, float r, bool loop, void* d_scratch,
+                       int out_t, bool coo, void* d_edge_out, float* d_vec_out);
+
 // Periodic radius-graph fetch (DeviceStore::gather_radius_graph_pbc): as
 // above, with the translated images of every node. d_cell is the (nidx, 9)
 // array of cell_t (DDS_F32 or DDS_F64) the fixed-stride gather has just

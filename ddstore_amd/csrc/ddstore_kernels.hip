@@ -2591,6 +2591,492 @@ const GatherKnobs& gather_knobs() {
 }
 
 // ---------------------------------------------------------------------------
+// Cell-list path of the open radius-graph fetch (algorithm = "cells"): the
+// same edges, order and outputs as k_radius_count / k_radius_fill, found in
+// O(nodes) by a spatial grid per graph, with one large graph spread over the
+// whole device. It stands where radius_count and radius_fill stand; k_radius_scan
+// and k_graph_fill are reused as they are.
+//
+// Binning, a superset of the rule's edges for every float32 input. A pair
+// passes only if fl(dx*dx) <= d2 <= r2 (sums of non-negative terms never round
+// below a term), so |dx| <= max(sqrt(r2), 2^-63) (1 + 2^-23), the second bound
+// where dx*dx or r2 is subnormal, and dx = fl(x_i - x_j) is within 2^-24 of the
+// real difference. With w0 = max(r, 2^-62) that is |x_i - x_j| <= w0 (1 + 2^-22).
+// The bin width is w = w0 (1 + 2^-10) and the bin coordinate q = floor(x / w),
+// both in float64, where the float32 x is exact and the quotient carries one
+// rounding of 2^-53 |x / w|. For |x / w| <= 2^40 two passing coordinates give
+// quotients at most (1 - 2^-11) + 2 * 2^-13 < 1 apart, so their floors differ by
+// at most 1. The quotient is clamped (monotonically) to +-2^40: float32 values
+// that large are spaced 2^16 w or more apart, so two of them, or one of them
+// and a smaller one, pass only when they are equal, and equal coordinates get
+// equal bins. The same holds on each axis, so every edge joins a bin with one
+// of its 27 neighbours. When r2 overflows to +inf every pair without a NaN
+// passes and all such nodes share one bin. Otherwise a node with a NaN or
+// infinite coordinate has no neighbour; it gets no bin and is left out of the
+// box. FP64 is used for binning only, never in the test.
+//
+// Grid. Bin coordinates are taken relative to the graph's minimum and the
+// graph's n nodes get at most n + 1 bins, graph s those from ptr[s] + s of one
+// flat array: no allocation pass, and Ncap + nidx bins bound the scratch
+// whatever the coordinates are. A box with more bins (two clusters far apart,
+// an outlier at 1e30) is coarsened by an integer right shift per axis, the
+// largest axis first; a shift keeps neighbours neighbours.
+//
+// Pipeline, all flat over the nodes of the whole batch (a node finds its graph
+// by a binary search of ptr), on grids sized by the nodes:
+//   k_cells_init     boxes, degrees and bin counts cleared
+//   k_cells_box      per-graph min / max of q: a wave of one graph reduces
+//                    across its lanes and issues six integer atomics
+//   k_cells_grid     per graph: origin, shifts and dimensions
+//   k_cells_hist     bin of every node, and its slot in the bin from an
+//                    integer atomicAdd (the order inside a bin is arbitrary;
+//                    the output does not depend on it)
+//   k_cells_scan_*   bin starts: tile sums, one block over the sums, apply; no
+//                    block waits for another
+//   k_cells_scatter  (x, y, z as f32, node id), 16 B per node, in bin order
+//   k_cells_count    a lane owns a dst, in bin order so that the lanes of a
+//                    wave read the same few bins: it walks the 9 rows of its
+//                    27 neighbour bins (x runs fastest, so a row's three bins
+//                    are one contiguous range of 16-B records) and writes
+//                    min(hits, K)
+//   k_cells_scan_*   the same three kernels over the degrees: every node's
+//                    first edge slot, 64-bit
+//   k_cells_counts   per-graph totals for k_radius_scan
+//   k_cells_fill     the walk again; every dst writes its run
+//
+// Edge order. Hits arrive in bin order. The fill keeps a dst's kept sources in
+// a private column of LDS (kCellsSortMax ids per lane, the column stride is
+// the block, so lanes never share a bank) by insertion: with a degree d <=
+// kCellsSortMax the column holds the d smallest ids seen so far, which is the
+// K cut and the order at once, and the run is then written ascending; the edge
+// vector of a written edge is recomputed from the packed positions by the same
+// subtraction. A dst with more kept edges than a column ranks every hit by a
+// second walk counting the hits with a smaller id and writes it at its rank:
+// exact, and quadratic in the dst's candidates (thousands of atoms within r of
+// each other without a K cap). LDS: 64 KiB per block, two blocks per CU; the
+// count pass uses none. Candidates are read from global memory: the lanes of a
+// wave share their rows, so the loads coalesce to a few lines from L2.
+//
+// Not done: staging a bin run's candidate rows in LDS for broadcast reads,
+// more than one dst per lane, an early exit of the count pass at K, and the
+// choice of algorithm per graph inside one call, which is the next step: a
+// batch mixing small and large graphs runs every graph on one path today.
+//
+// Measured on MI355X (profiles/radius_cells_ab.txt), 4.5 nodes per unit volume,
+// r = 1.0, f32, int64 ids, exact capacities, the whole fetch: one graph of 256
+// / 1 k / 4 k / 16 k nodes 0.18 / 0.23 / 0.26 / 0.30 ms against 0.15 / 1.9 /
+// 28.5 / 442 ms for the brute-force kernels; 64 k and 256 k nodes 0.39 and
+// 0.92 ms; 64 graphs of 2 k nodes 0.32 against 7.9 ms. Edge vectors add up to
+// 9 %. The crossover lies between 256 and 1 k nodes, so kCellsMinNodes is its
+// floor of 1024. The fourteen launches of the count side are most of the time
+// below 16 k nodes; the per-kernel split was not measured, and neither were
+// other densities, f64 positions, int32 ids or a K cap. The fill kernel uses
+// up to 47 VGPRs and 64 KiB of LDS, the count kernel 31 VGPRs and none, no
+// kernel has scratch.
+// ---------------------------------------------------------------------------
+
+constexpr int kCellsSortMax = 64;     // ids a lane's LDS column holds
+constexpr int kCellsMinNodes = 1024;  // "auto" takes this path from here on
+constexpr int kCellsScanPer = 8;      // elements per thread of a scan tile
+constexpr int kCellsScanTile = kBlock * kCellsScanPer;
+constexpr double kCellsClamp = 1099511627776.0;  // 2^40
+constexpr uint32_t kCellsNoBin = 0xFFFFFFFFu;
+
+struct CellsGrid {  // one graph's grid: bin = ((q - lo) >> sh) per axis
+    int64_t lo[3];
+    int32_t sh[3];
+    int32_t dim[3];
+};
+static_assert(sizeof(CellsGrid) == 48, "radius_cells_scratch_bytes counts 48 bytes");
+
+struct alignas(16) CellsNode {  // a node in bin order
+    float x, y, z;
+    int32_t id;  // its row of the packed positions
+};
+
+// Bin width and the r2 = +inf case (see the section note).
+struct CellsBinning {
+    double w;
+    bool all;
+};
+
+// The bin coordinate of one f32 coordinate; false for a node that has no bin.
+__device__ __forceinline__ bool cells_coord(float x, const CellsBinning& bn, int64_t& q) {
+    if (bn.all) {
+        q = 0;
+        return x == x;
+    }
+    if (!(__builtin_fabsf(x) <= 3.402823466e+38f)) return false;
+    double t = floor((double)x / bn.w);
+    t = t < -kCellsClamp ? -kCellsClamp : (t > kCellsClamp ? kCellsClamp : t);
+    q = (int64_t)t;
+    return true;
+}
+
+template <typename Tin>
+__device__ __forceinline__ bool cells_node_q(const Tin* __restrict__ pos, int64_t i,
+                                             const CellsBinning& bn, int64_t (&q)[3]) {
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok &= cells_coord(radius_coord(pos[3 * i + a]), bn, q[a]);
+    return ok;
+}
+
+// The graph of packed row i: the s with ptr[s] <= i < ptr[s+1] if its nodes
+// were kept (ptr[s+1] <= ncap), or -1.
+__device__ __forceinline__ int64_t cells_graph_of(const int64_t* __restrict__ ptr,
+                                                  int64_t nidx, int64_t ncap, int64_t i) {
+    int64_t lo = 0, hi = nidx;  // the largest s in [0, nidx] with ptr[s] <= i
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (ptr[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo < nidx && ptr[lo] <= i && ptr[lo + 1] <= ncap ? lo : -1;
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_cells_init(int64_t nidx, int64_t ncap, int64_t nbins, int64_t* __restrict__ box,
+             int32_t* __restrict__ deg, int32_t* __restrict__ bins) {
+    const int64_t gt = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = gt; i < 6 * nidx; i += nt) box[i] = i % 6 < 3 ? INT64_MAX : INT64_MIN;
+    for (int64_t i = gt; i <= ncap; i += nt) deg[i] = 0;
+    for (int64_t i = gt; i <= nbins; i += nt) bins[i] = 0;
+}
+
+// box[6 s ..] = min q (3), max q (3) over the nodes of graph s that have a bin.
+template <typename Tin>
+__global__ void __launch_bounds__(kBlock)
+k_cells_box(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr, int64_t nidx,
+            int64_t ncap, CellsBinning bn, int64_t* __restrict__ box) {
+    // whole waves run every round, so the shuffles see all 64 lanes
+    for (int64_t base = (int64_t)blockIdx.x * kBlock; base < ncap;
+         base += (int64_t)gridDim.x * kBlock) {
+        const int64_t i = base + threadIdx.x;
+        int64_t s = -1, q[3] = {0, 0, 0};
+        bool ok = false;
+        if (i < ncap) {
+            s = cells_graph_of(ptr, nidx, ncap, i);
+            if (s >= 0) ok = cells_node_q(pos, i, bn, q);
+        }
+        const int64_t s0 = __shfl((long long)s, 0);
+        if (__all(s == s0)) {
+            if (s0 < 0) continue;  // wave-uniform
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                int64_t mn = ok ? q[a] : INT64_MAX, mx = ok ? q[a] : INT64_MIN;
+                for (int off = 32; off > 0; off >>= 1) {
+                    const int64_t on = __shfl_xor((long long)mn, off);
+                    const int64_t ox = __shfl_xor((long long)mx, off);
+                    mn = on < mn ? on : mn;
+                    mx = ox > mx ? ox : mx;
+                }
+                if ((threadIdx.x & 63) == 0 && mn != INT64_MAX) {
+                    atomicMin((long long*)&box[6 * s0 + a], (long long)mn);
+                    atomicMax((long long*)&box[6 * s0 + 3 + a], (long long)mx);
+                }
+            }
+        } else if (ok) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                atomicMin((long long*)&box[6 * s + a], (long long)q[a]);
+                atomicMax((long long*)&box[6 * s + 3 + a], (long long)q[a]);
+            }
+        }
+    }
+}
+
+// Origin, shifts and dimensions of every graph: the box, its largest axis
+// halved until the bins fit the graph's n + 1. The product is compared in
+// f64: exact where it decides (at or under the budget), monotone above.
+__global__ void __launch_bounds__(kBlock)
+k_cells_grid(const int64_t* __restrict__ ptr, int64_t nidx, int64_t ncap,
+             const int64_t* __restrict__ box, CellsGrid* __restrict__ grid) {
+    const int64_t nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < nidx; s += nt) {
+        CellsGrid g = {{0, 0, 0}, {0, 0, 0}, {1, 1, 1}};
+        const int64_t n = ptr[s + 1] - ptr[s];
+        if (n > 0 && ptr[s + 1] <= ncap && box[6 * s] != INT64_MAX) {
+            int64_t ext[3], d[3];
+            for (int a = 0; a < 3; ++a) {
+                g.lo[a] = box[6 * s + a];
+                ext[a] = box[6 * s + 3 + a] - g.lo[a];  // <= 2^41
+            }
+            const double budget = (double)(n + 1);
+            for (;;) {
+                for (int a = 0; a < 3; ++a) d[a] = (ext[a] >> g.sh[a]) + 1;
+                if ((double)d[0] * (double)d[1] * (double)d[2] <= budget) break;
+                int m = d[1] > d[0] ? 1 : 0;
+                if (d[2] > d[m]) m = 2;
+                ++g.sh[m];
+            }
+            for (int a = 0; a < 3; ++a) g.dim[a] = (int32_t)d[a];
+        }
+        grid[s] = g;
+    }
+}
+
+// bin_of[i] = the flat bin of packed row i (kCellsNoBin without one) and
+// slot[i] its place among the nodes of that bin; bins[] counts.
+template <typename Tin>
+__global__ void __launch_bounds__(kBlock)
+k_cells_hist(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr, int64_t nidx,
+             int64_t ncap, CellsBinning bn, const CellsGrid* __restrict__ grid,
+             uint32_t* __restrict__ bin_of, uint32_t* __restrict__ slot,
+             int32_t* __restrict__ bins) {
+    const int64_t nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ncap; i += nt) {
+        uint32_t b = kCellsNoBin;
+        const int64_t s = cells_graph_of(ptr, nidx, ncap, i);
+        int64_t q[3];
+        if (s >= 0 && cells_node_q(pos, i, bn, q)) {
+            const CellsGrid g = grid[s];
+            int64_t c[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) c[a] = (q[a] - g.lo[a]) >> g.sh[a];
+            b = (uint32_t)(ptr[s] + s + c[0] + g.dim[0] * (c[1] + g.dim[1] * c[2]));
+            slot[i] = (uint32_t)atomicAdd(&bins[b], 1);
+        }
+        bin_of[i] = b;
+    }
+}
+
+// Exclusive scan of in[0, n) into out[0, n) (which may be `in`), three
+// launches: the sum of every tile, an exclusive scan of the sums by ONE block,
+// and the tiles again with their offset.
+template <typename Tin>
+__global__ void __launch_bounds__(kBlock)
+k_cells_scan_sums(const Tin* in, int64_t n, int64_t* __restrict__ sums) {
+    __shared__ int64_t s_w[kBlock / 64];
+    const int64_t i0 = (int64_t)blockIdx.x * kCellsScanTile + threadIdx.x * kCellsScanPer;
+    int64_t x = 0;
+#pragma unroll
+    for (int k = 0; k < kCellsScanPer; ++k) x += i0 + k < n ? (int64_t)in[i0 + k] : 0;
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor((long long)x, off);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t t = 0;
+        for (int w = 0; w < kBlock / 64; ++w) t += s_w[w];
+        sums[blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_cells_scan_top(int64_t* __restrict__ sums, int64_t tiles) {
+    __shared__ int64_t s_wsum2[2 * (kBlock / 64)];
+    __shared__ int64_t s_tot[2];
+    int64_t carry = 0;
+    for (int64_t base = 0; base < tiles; base += kBlock) {
+        const int64_t i = base + threadIdx.x;
+        const int64_t v = i < tiles ? sums[i] : 0;
+        int64_t x = v, y = 0;
+        block_scan_pair(x, y, s_wsum2, threadIdx.x & 63, threadIdx.x >> 6, s_tot);
+        if (i < tiles) sums[i] = carry + x - v;
+        carry += s_tot[0];
+        __syncthreads();  // LDS reused next round
+    }
+}
+
+template <typename Tin, typename Tout>
+__global__ void __launch_bounds__(kBlock)
+k_cells_scan_apply(const Tin* in, int64_t n, const int64_t* __restrict__ sums, Tout* out) {
+    __shared__ int64_t s_wsum2[2 * (kBlock / 64)];
+    const int64_t i0 = (int64_t)blockIdx.x * kCellsScanTile + threadIdx.x * kCellsScanPer;
+    int64_t v[kCellsScanPer], x = 0, y = 0;
+#pragma unroll
+    for (int k = 0; k < kCellsScanPer; ++k) {
+        v[k] = i0 + k < n ? (int64_t)in[i0 + k] : 0;
+        x += v[k];
+    }
+    const int64_t mine = x;
+    block_scan_pair(x, y, s_wsum2, threadIdx.x & 63, threadIdx.x >> 6, nullptr);
+    int64_t run = sums[blockIdx.x] + x - mine;
+#pragma unroll
+    for (int k = 0; k < kCellsScanPer; ++k) {
+        if (i0 + k < n) out[i0 + k] = (Tout)run;
+        run += v[k];
+    }
+}
+
+template <typename Tin>
+__global__ void __launch_bounds__(kBlock)
+k_cells_scatter(const Tin* __restrict__ pos, int64_t ncap,
+                const uint32_t* __restrict__ bin_of, const uint32_t* __restrict__ slot,
+                const int32_t* __restrict__ bin_start, CellsNode* __restrict__ sorted) {
+    const int64_t nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ncap; i += nt) {
+        const uint32_t b = bin_of[i];
+        if (b == kCellsNoBin) continue;
+        sorted[(int64_t)bin_start[b] + slot[i]] =
+            CellsNode{radius_coord(pos[3 * i]), radius_coord(pos[3 * i + 1]),
+                      radius_coord(pos[3 * i + 2]), (int32_t)i};
+    }
+}
+
+// What a dst needs for its walk: itself and the up to nine rows of bins
+// around it, every row one contiguous range of `sorted` (scalars, not arrays:
+// an indexed array would live in scratch memory).
+struct CellsDst {
+    CellsNode c;
+    int64_t row0;          // flat bin (0, y0, z0) of the graph's grid
+    int32_t x0, x1;        // bins x0 .. x1 of every row
+    int32_t ny, nz;        // rows y0 .. y0 + ny - 1, likewise z
+    int32_t dimx, dimy;
+};
+
+__device__ __forceinline__ CellsDst cells_dst(const CellsNode* __restrict__ sorted,
+                                              const int64_t* __restrict__ ptr,
+                                              int64_t nidx, int64_t ncap,
+                                              const CellsGrid* __restrict__ grid,
+                                              const uint32_t* __restrict__ bin_of,
+                                              int64_t t) {
+    CellsDst d;
+    d.c = sorted[t];
+    const int64_t s = cells_graph_of(ptr, nidx, ncap, d.c.id);  // kept: it has a bin
+    const int32_t dx = grid[s].dim[0], dy = grid[s].dim[1], dz = grid[s].dim[2];
+    const int64_t g0 = ptr[s] + s;
+    const uint32_t rel = (uint32_t)(bin_of[d.c.id] - g0);
+    const int32_t bx = (int32_t)(rel % (uint32_t)dx), rest = (int32_t)(rel / (uint32_t)dx);
+    const int32_t by = rest % dy, bz = rest / dy;
+    const int32_t y0 = by > 0 ? by - 1 : 0, y1 = by + 1 < dy ? by + 1 : dy - 1;
+    const int32_t z0 = bz > 0 ? bz - 1 : 0, z1 = bz + 1 < dz ? bz + 1 : dz - 1;
+    d.x0 = bx > 0 ? bx - 1 : 0;
+    d.x1 = bx + 1 < dx ? bx + 1 : dx - 1;
+    d.ny = y1 - y0 + 1;
+    d.nz = z1 - z0 + 1;
+    d.dimx = dx;
+    d.dimy = dy;
+    d.row0 = g0 + ((int64_t)z0 * dy + y0) * dx;
+    return d;
+}
+
+// Every candidate of the dst that passes the rule: hit(id, dx, dy, dz), id the
+// source's packed row, in bin order.
+template <typename Hit>
+__device__ __forceinline__ void cells_walk(const CellsNode* __restrict__ sorted,
+                                           const int32_t* __restrict__ bin_start,
+                                           const CellsDst& d, float r2, bool loop,
+                                           Hit&& hit) {
+#pragma clang fp contract(off)
+    for (int32_t z = 0; z < d.nz; ++z) {
+        for (int32_t y = 0; y < d.ny; ++y) {
+            const int64_t row = d.row0 + ((int64_t)z * d.dimy + y) * d.dimx;
+            const int32_t end = bin_start[row + d.x1 + 1];
+            for (int32_t u = bin_start[row + d.x0]; u < end; ++u) {
+                const CellsNode m = sorted[u];
+                const float dx = m.x - d.c.x, dy = m.y - d.c.y, dz = m.z - d.c.z;
+                const float d2 = (dx * dx + dy * dy) + dz * dz;
+                if (d2 <= r2 && (loop || m.id != d.c.id)) hit(m.id, dx, dy, dz);
+            }
+        }
+    }
+}
+
+// deg[i] = min(neighbours of packed row i, kcap) for every node with a bin
+// (the others keep k_cells_init's 0). `total` is bin_start's last entry.
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_cells_count(const CellsNode* __restrict__ sorted, const int32_t* __restrict__ bin_start,
+              const int32_t* __restrict__ total, const int64_t* __restrict__ ptr,
+              int64_t nidx, int64_t ncap, const CellsGrid* __restrict__ grid,
+              const uint32_t* __restrict__ bin_of, float r2, int kcap, bool loop,
+              int32_t* __restrict__ deg) {
+    const int64_t m = *total, nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < m; t += nt) {
+        const CellsDst d = cells_dst(sorted, ptr, nidx, ncap, grid, bin_of, t);
+        int cnt = 0;
+        cells_walk(sorted, bin_start, d, r2, loop, [&](int32_t, float, float, float) { ++cnt; });
+        deg[d.c.id] = cnt < kcap ? cnt : kcap;
+    }
+}
+
+// counts[s] = the edges of graph s: its nodes' degrees, from their scan `off`.
+__global__ void __launch_bounds__(kBlock)
+k_cells_counts(const int64_t* __restrict__ ptr, int64_t nidx, int64_t ncap,
+               const int64_t* __restrict__ off, int64_t* __restrict__ counts) {
+    const int64_t nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < nidx; s += nt) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1];
+        counts[s] = p1 > p0 && p0 >= 0 && p1 <= ncap ? off[p1] - off[p0] : 0;
+    }
+}
+
+template <typename Tout, bool COO>
+__device__ __forceinline__ void cells_store(Tout* __restrict__ out, int64_t ecap,
+                                            int64_t o, int64_t src, int64_t dst) {
+    const Tout a = static_cast<Tout>(src), b = static_cast<Tout>(dst);
+    if constexpr (COO) {
+        out[o] = a;
+        out[ecap + o] = b;
+    } else {
+        reinterpret_cast<IdPair<Tout>*>(out)[o] = IdPair<Tout>{a, b};
+    }
+}
+
+// The edges of every graph k_radius_fill would write, in its layout: dst
+// `i`'s run starts at off[i] (the scan of the degrees, which for a kept graph
+// is edge_ptr[s] plus the degrees in front of i) and holds off[i+1] - off[i]
+// edges, sources ascending. See the section note for the two orderings.
+template <typename Tin, typename Tout, bool COO, bool VEC>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_cells_fill(const Tin* __restrict__ pos, const CellsNode* __restrict__ sorted,
+             const int32_t* __restrict__ bin_start, const int32_t* __restrict__ total,
+             const int64_t* __restrict__ ptr, const int64_t* __restrict__ edge_ptr,
+             int64_t nidx, int64_t ncap, int64_t ecap, const CellsGrid* __restrict__ grid,
+             const uint32_t* __restrict__ bin_of, const int64_t* __restrict__ off, float r2,
+             bool loop, Tout* __restrict__ out, float* __restrict__ vec) {
+#pragma clang fp contract(off)
+    __shared__ int32_t s_ids[kCellsSortMax * kBlock];
+    int32_t* col = s_ids + threadIdx.x;  // entry k at col[k * kBlock]
+    const int64_t m = *total, nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < m; t += nt) {
+        const int32_t i = sorted[t].id;
+        const int64_t o0 = off[i];
+        const int64_t d = off[i + 1] - o0;
+        if (d <= 0) continue;
+        const int64_t s = cells_graph_of(ptr, nidx, ncap, i);
+        if (edge_ptr[s + 1] > ecap || o0 < 0) continue;  // this graph's edges are not kept
+        const CellsDst ds = cells_dst(sorted, ptr, nidx, ncap, grid, bin_of, t);
+        if (d <= kCellsSortMax) {
+            const int cap = (int)d;
+            int cnt = 0;
+            cells_walk(sorted, bin_start, ds, r2, loop, [&](int32_t id, float, float, float) {
+                int p;
+                if (cnt < cap) p = cnt++;
+                else if (id < col[(cap - 1) * kBlock]) p = cap - 1;
+                else return;
+                for (; p > 0 && col[(p - 1) * kBlock] > id; --p)
+                    col[p * kBlock] = col[(p - 1) * kBlock];
+                col[p * kBlock] = id;
+            });
+            for (int k = 0; k < cnt; ++k) {
+                const int64_t src = col[k * kBlock];
+                cells_store<Tout, COO>(out, ecap, o0 + k, src, i);
+                if constexpr (VEC) {
+                    vec[3 * (o0 + k)] = radius_coord(pos[3 * src]) - ds.c.x;
+                    vec[3 * (o0 + k) + 1] = radius_coord(pos[3 * src + 1]) - ds.c.y;
+                    vec[3 * (o0 + k) + 2] = radius_coord(pos[3 * src + 2]) - ds.c.z;
+                }
+            }
+        } else {
+            cells_walk(sorted, bin_start, ds, r2, loop, [&](int32_t id, float dx, float dy, float dz) {
+                int64_t rank = 0;
+                cells_walk(sorted, bin_start, ds, r2, loop,
+                           [&](int32_t other, float, float, float) { rank += other < id; });
+                if (rank >= d) return;  // the K cut
+                cells_store<Tout, COO>(out, ecap, o0 + rank, id, i);
+                if constexpr (VEC) {
+                    vec[3 * (o0 + rank)] = dx;
+                    vec[3 * (o0 + rank) + 1] = dy;
+                    vec[3 * (o0 + rank) + 2] = dz;
+                }
+            });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Triplet index (DeviceStore::build_triplets): for every kept edge e = (j ->
 // i) of a radius-graph batch the edges e' = (k -> j), without the one way
 // straight back to i through the same image. Both fetches order a graph's
@@ -3531,6 +4017,145 @@ void radius_fill(hipStream_t stream, const void* d_pos, int pos_t,
         if (pos_t == DDS_F64) launch_out(TypeTag<double>{}, G);
         else if (pos_t == DDS_F32) launch_out(TypeTag<float>{}, G);
     });
+}
+
+int radius_cells_sort_max() { return kCellsSortMax; }
+
+int radius_cells_min_nodes() { return kCellsMinNodes; }
+
+namespace {
+
+// Scratch of the cell-list path, every part 16-byte aligned.
+struct CellsScratch {
+    CellsNode* sorted;   // [ncap]
+    int64_t* counts;     // [nidx + 1]
+    int64_t* off;        // [ncap + 1]
+    int64_t* box;        // [6 nidx]
+    CellsGrid* grid;     // [nidx]
+    int64_t* sums;       // [tiles of the larger scan]
+    int32_t* deg;        // [ncap + 1]
+    uint32_t* bin_of;    // [ncap]
+    uint32_t* slot;      // [ncap]
+    int32_t* bins;       // [nbins + 1], counts and then starts
+    int64_t nbins;
+    size_t bytes;
+};
+
+CellsScratch cells_scratch(void* base, int64_t nidx, int64_t ncap) {
+    CellsScratch s;
+    s.nbins = ncap + nidx;
+    char* p = reinterpret_cast<char*>(base);
+    auto take = [&](auto*& field, int64_t n) {
+        using T = std::remove_pointer_t<std::remove_reference_t<decltype(field)>>;
+        field = reinterpret_cast<T*>(p);
+        p += ((size_t)n * sizeof(T) + 15) / 16 * 16;
+    };
+    take(s.sorted, ncap);
+    take(s.counts, nidx + 1);
+    take(s.off, ncap + 1);
+    take(s.box, 6 * nidx);
+    take(s.grid, nidx);
+    take(s.sums, (s.nbins + 1) / kCellsScanTile + 1);
+    take(s.deg, ncap + 1);
+    take(s.bin_of, ncap);
+    take(s.slot, ncap);
+    take(s.bins, s.nbins + 1);
+    s.bytes = (size_t)(p - reinterpret_cast<char*>(base));
+    return s;
+}
+
+int cells_blocks(int64_t n) {
+    const int64_t b = (n + kBlock - 1) / kBlock;
+    const int64_t cap = (int64_t)cu_count() * kBlocksPerCU;
+    return (int)(b < 1 ? 1 : (b < cap ? b : cap));
+}
+
+template <typename Tin, typename Tout>
+void cells_scan(hipStream_t stream, const Tin* in, int64_t n, int64_t* sums, Tout* out) {
+    const int64_t tiles = (n + kCellsScanTile - 1) / kCellsScanTile;
+    hipLaunchKernelGGL((k_cells_scan_sums<Tin>), dim3((unsigned)tiles), dim3(kBlock), 0,
+                       stream, in, n, sums);
+    hipLaunchKernelGGL(k_cells_scan_top, dim3(1), dim3(kBlock), 0, stream, sums, tiles);
+    hipLaunchKernelGGL((k_cells_scan_apply<Tin, Tout>), dim3((unsigned)tiles),
+                       dim3(kBlock), 0, stream, in, n, sums, out);
+}
+
+}  // namespace
+
+// 36 bytes per node, 4 per bin (ncap + nidx of them), 104 per graph and 8 per
+// scan tile, each part rounded up to 16: under 112 * (ncap + nidx) + 256.
+size_t radius_cells_scratch_bytes(int64_t nidx, int64_t ncap) {
+    return cells_scratch(nullptr, nidx, ncap).bytes;
+}
+
+void radius_cells_count(hipStream_t stream, const void* d_pos, int pos_t,
+                        const int64_t* d_ptr, int64_t nidx, int64_t ncap, float r,
+                        int64_t max_neighbors, bool loop, void* d_scratch,
+                        int64_t* d_edge_ptr) {
+    if (nidx == 0 || (pos_t != DDS_F32 && pos_t != DDS_F64)) return;
+    const CellsScratch sc = cells_scratch(d_scratch, nidx, ncap);
+    const float r2 = r * r;
+    const double w0 = (double)r > 0x1p-62 ? (double)r : 0x1p-62;
+    const CellsBinning bn = {w0 * (1.0 + 0x1p-10), std::isinf(r2)};
+    const int kcap = max_neighbors > 0 && max_neighbors < INT32_MAX
+                         ? (int)max_neighbors : INT32_MAX;
+    const int by_node = cells_blocks(ncap), by_graph = cells_blocks(nidx);
+    hipLaunchKernelGGL(k_cells_init, dim3(cells_blocks(sc.nbins + 1)), dim3(kBlock), 0,
+                       stream, nidx, ncap, sc.nbins, sc.box, sc.deg, sc.bins);
+    auto typed = [&](auto ti) {
+        using Tin = typename decltype(ti)::type;
+        const Tin* pos = (const Tin*)d_pos;
+        hipLaunchKernelGGL((k_cells_box<Tin>), dim3(by_node), dim3(kBlock), 0, stream, pos,
+                           d_ptr, nidx, ncap, bn, sc.box);
+        hipLaunchKernelGGL(k_cells_grid, dim3(by_graph), dim3(kBlock), 0, stream, d_ptr,
+                           nidx, ncap, sc.box, sc.grid);
+        hipLaunchKernelGGL((k_cells_hist<Tin>), dim3(by_node), dim3(kBlock), 0, stream, pos,
+                           d_ptr, nidx, ncap, bn, sc.grid, sc.bin_of, sc.slot, sc.bins);
+        cells_scan<int32_t, int32_t>(stream, sc.bins, sc.nbins + 1, sc.sums, sc.bins);
+        hipLaunchKernelGGL((k_cells_scatter<Tin>), dim3(by_node), dim3(kBlock), 0, stream,
+                           pos, ncap, sc.bin_of, sc.slot, sc.bins, sc.sorted);
+    };
+    if (pos_t == DDS_F64) typed(TypeTag<double>{});
+    else typed(TypeTag<float>{});
+    hipLaunchKernelGGL(k_cells_count, dim3(by_node), dim3(kBlock), 0, stream, sc.sorted,
+                       sc.bins, sc.bins + sc.nbins, d_ptr, nidx, ncap, sc.grid, sc.bin_of,
+                       r2, kcap, loop, sc.deg);
+    cells_scan<int32_t, int64_t>(stream, sc.deg, ncap + 1, sc.sums, sc.off);
+    hipLaunchKernelGGL(k_cells_counts, dim3(by_graph), dim3(kBlock), 0, stream, d_ptr, nidx,
+                       ncap, sc.off, sc.counts);
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, sc.counts, nidx,
+                       d_edge_ptr);
+}
+
+void radius_cells_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                       const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                       int64_t ncap, int64_t ecap, float r, bool loop, void* d_scratch,
+                       int out_t, bool coo, void* d_edge_out, float* d_vec_out) {
+    if (nidx == 0 || ecap == 0 || ncap == 0) return;
+    const CellsScratch sc = cells_scratch(d_scratch, nidx, ncap);
+    const float r2 = r * r;
+    const int grid = cells_blocks(ncap);
+    auto launch = [&](auto ti, auto to, auto c, auto v) {
+        using Tin = typename decltype(ti)::type;
+        using Tout = typename decltype(to)::type;
+        hipLaunchKernelGGL((k_cells_fill<Tin, Tout, decltype(c)::value, decltype(v)::value>),
+                           dim3(grid), dim3(kBlock), 0, stream, (const Tin*)d_pos, sc.sorted,
+                           sc.bins, sc.bins + sc.nbins, d_ptr, d_edge_ptr, nidx, ncap, ecap,
+                           sc.grid, sc.bin_of, sc.off, r2, loop, (Tout*)d_edge_out,
+                           d_vec_out);
+    };
+    auto launch_flags = [&](auto ti, auto to) {
+        if (coo && d_vec_out) launch(ti, to, std::true_type{}, std::true_type{});
+        else if (coo) launch(ti, to, std::true_type{}, std::false_type{});
+        else if (d_vec_out) launch(ti, to, std::false_type{}, std::true_type{});
+        else launch(ti, to, std::false_type{}, std::false_type{});
+    };
+    auto launch_out = [&](auto ti) {
+        if (out_t == DDS_I64) launch_flags(ti, TypeTag<int64_t>{});
+        else if (out_t == DDS_I32) launch_flags(ti, TypeTag<int32_t>{});
+    };
+    if (pos_t == DDS_F64) launch_out(TypeTag<double>{});
+    else if (pos_t == DDS_F32) launch_out(TypeTag<float>{});
 }
 
 // Scratch of the periodic call: counts, the boxes, then in nearest mode the

@@ -1238,6 +1238,7 @@ class DDStore:
         edge_fill: int = -1,
         edge_vec: bool = False,
         node_extras: Sequence[str] = (),
+        algorithm: str = "auto",
     ) -> RadiusGraphBatch:
         """Fetch a minibatch of whole graphs whose edges are a function of the
         node positions: every pair of nodes of one graph within the cutoff
@@ -1302,8 +1303,26 @@ class DDStore:
         together or not at all. Without them ``Ncap`` is sized from the host
         offsets and ``Ecap`` exactly, which takes one read-back of
         ``edge_ptr[-1]`` between counting and writing the edges: that path
-        syncs with the device, the capacity path does not."""
+        syncs with the device, the capacity path does not.
+
+        ``algorithm`` (``"auto"``, ``"brute"`` or ``"cells"``, anything else:
+        ``ValueError``) chooses how the device finds the edges; the result is
+        the same bit for bit. ``"brute"`` tests every pair of a graph, one
+        lane group per graph. ``"cells"`` bins every graph's nodes into a
+        spatial grid and tests the 27 neighbouring bins of each node, O(nodes)
+        and with one large graph spread over the whole device; it has no
+        nearest cap (``nearest=True``: ``ValueError``) and needs ``Ncap + n <
+        2**31``. ``"auto"`` takes ``"cells"`` iff ``nearest`` is false and the
+        variable's largest sample has at least ``_C.RADIUS_CELLS_MIN_NODES``
+        nodes (from the host offsets, once per variable, no sync), else
+        ``"brute"``. The host backend checks the argument and ignores it."""
         what = "get_radius_graph_batch"
+        if algorithm not in ("auto", "brute", "cells"):
+            raise ValueError(
+                f"ddstore {what}: algorithm must be 'auto', 'brute' or 'cells'")
+        if algorithm == "cells" and nearest:
+            raise ValueError(
+                f"ddstore {what}: algorithm='cells' has no nearest cap")
         self._refuse_mx(what, pos_name)
         meta = self._meta(pos_name)
         if (not meta["is_csr"] or meta["disp"] != 3
@@ -1368,9 +1387,11 @@ class DDStore:
         k = int(max_neighbors) if max_neighbors is not None else 0
         self._account(meta, idx)
         if self.mode == "hip":
+            cells = algorithm == "cells" or (
+                algorithm == "auto" and not nearest and self._cells_by_size(pos_name))
             ptr, edge_ptr, edge_out, vec_out = self._backend.gather_radius_graph(
                 pos_name, idx, float(rf), k, bool(loop), pos_out, edge_out, batch_out,
-                vec_out, bool(edge_vec), sized, bool(coo), fill, bool(nearest))
+                vec_out, bool(edge_vec), sized, bool(coo), fill, bool(nearest), cells)
         else:
             ptr, edge_ptr, edge_out, vec_out = self._radius_graph_host(
                 pos_name, idx, rf, k, bool(loop), pos_out, edge_out, batch_out,
@@ -1381,6 +1402,18 @@ class DDStore:
             ptr, edge_ptr, batch_out.view(ncap),
             vec_out.view(ecap, 3) if edge_vec else None,
             tuple(self.get_csr(nm, idx) for nm in node_extras))
+
+    def _cells_by_size(self, name):
+        """Whether ``algorithm="auto"`` takes the cell-list path for this
+        variable: its largest sample, from the host offsets, once."""
+        key = (name, "cells")
+        if key not in self._graph_extras_ok:
+            from . import _C
+
+            goff = self._meta(name)["goff"]
+            most = int((goff[1:] - goff[:-1]).max()) if goff.numel() > 1 else 0
+            self._graph_extras_ok[key] = most >= _C.RADIUS_CELLS_MIN_NODES
+        return self._graph_extras_ok[key]
 
     def _check_nearest(self, what, k, name, images):
         """The nearest cap's ``K``, and once per variable and image count that
