@@ -1089,7 +1089,10 @@ public:
     // vec_out, cell, shifts_needed); shifts_needed is int32 (n, 3). shift_out
     // and vec_out are written only on rows of kept edges, a bad index leaves
     // its cell row untouched. max_neighbors != 0 is the nearest cap (the caller
-    // has checked nodes * images < 2^32 for the variable).
+    // has checked nodes * images < 2^32 for the variable). With `cells` (not
+    // with the nearest cap; the same check, and Ncap + n < 2^31) the cell-list
+    // launchers radius_pbc_cells_count / radius_pbc_cells_fill stand for
+    // radius_pbc_count / radius_pbc_fill: the same outputs bit for bit.
     std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                at::Tensor>
     gather_radius_graph_pbc(const std::string& pos_name, const std::string& cell_name,
@@ -1098,7 +1101,7 @@ public:
                             at::Tensor edge_out, at::Tensor batch_out,
                             at::Tensor shift_out, at::Tensor vec_out, bool edge_vec,
                             bool size_edges, bool coo, int64_t edge_fill,
-                            int64_t max_neighbors) {
+                            int64_t max_neighbors, bool cells) {
         RoctxRange rr_("ddstore::gather_radius_graph_pbc");
         const char* op = "ddstore gather_radius_graph_pbc: ";
         DeviceVar& pv = var(pos_name);
@@ -1123,8 +1126,11 @@ public:
         TORCH_CHECK(max_neighbors >= 0 && max_neighbors <= ddstore::radius_nearest_max(),
                     op, "max_neighbors is 0 (none) or in 1..",
                     ddstore::radius_nearest_max());
+        TORCH_CHECK(!(cells && nearest), op, "the cell-list path has no nearest cap");
         const int64_t nidx = idx.numel();
         const int64_t ncap = pos_out.numel() / 3;
+        TORCH_CHECK(!cells || ncap + nidx < (int64_t(1) << 31), op,
+                    "the cell-list path needs Ncap + n < 2^31");
         TORCH_CHECK(batch_out.scalar_type() == at::kLong && batch_out.is_contiguous() &&
                         batch_out.device().is_cuda() &&
                         batch_out.device().index() == device_ &&
@@ -1145,10 +1151,17 @@ public:
         at::Tensor edge_ptr = at::empty({nidx + 1}, opts);
         at::Tensor needed = at::empty({nidx, 3}, opts.dtype(at::kInt));
         at::Tensor scratch = at::empty(
-            {(int64_t)ddstore::radius_pbc_scratch_bytes(nidx, ncap, nearest)},
+            {(int64_t)(cells ? ddstore::radius_pbc_cells_scratch_bytes(nidx, ncap)
+                             : ddstore::radius_pbc_scratch_bytes(nidx, ncap, nearest))},
             opts.dtype(at::kByte));
         if (nidx == 0) {
             edge_ptr.zero_();
+        } else if (cells) {
+            ddstore::radius_pbc_cells_count(
+                stream(), pos_out.data_ptr(), pv.dds_t, cell.data_ptr(), cv.dds_t,
+                ptr.data_ptr<int64_t>(), idx.data_ptr<int64_t>(), nidx, pv.nrows_total(),
+                ncap, rf, (int)pbc, (int)max_shift, loop, scratch.data_ptr(),
+                edge_ptr.data_ptr<int64_t>(), needed.data_ptr<int32_t>());
         } else if (nearest) {
             ddstore::radius_pbc_nearest_select(
                 stream(), pos_out.data_ptr(), pv.dds_t, cell.data_ptr(), cv.dds_t,
@@ -1195,7 +1208,13 @@ public:
                             "elements on the store device");
             d_vec = ecap ? vec_out.data_ptr<float>() : nullptr;
         }
-        if (nidx > 0 && ecap > 0)
+        if (nidx > 0 && ecap > 0 && cells)
+            ddstore::radius_pbc_cells_fill(
+                stream(), pos_out.data_ptr(), pv.dds_t, ptr.data_ptr<int64_t>(),
+                edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, rf, loop,
+                scratch.data_ptr(), out_t, coo, edge_out.data_ptr(),
+                shift_out.data_ptr<int32_t>(), d_vec);
+        else if (nidx > 0 && ecap > 0)
             ddstore::radius_pbc_fill(
                 stream(), pos_out.data_ptr(), pv.dds_t, ptr.data_ptr<int64_t>(),
                 edge_ptr.data_ptr<int64_t>(), nidx, ncap, ecap, rf, (int)pbc, loop,

@@ -88,7 +88,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("gather_radius_graph", &DeviceStore::gather_radius_graph,
              py::call_guard<py::gil_scoped_release>())
         .def("gather_radius_graph_pbc", &DeviceStore::gather_radius_graph_pbc,
-             py::call_guard<py::gil_scoped_release>())
+             py::arg("pos_name"), py::arg("cell_name"), py::arg("idx"), py::arg("r"),
+             py::arg("pbc"), py::arg("max_shift"), py::arg("loop"), py::arg("pos_out"),
+             py::arg("edge_out"), py::arg("batch_out"), py::arg("shift_out"),
+             py::arg("vec_out"), py::arg("edge_vec"), py::arg("size_edges"),
+             py::arg("coo"), py::arg("edge_fill"), py::arg("max_neighbors"),
+             py::arg("cells") = false, py::call_guard<py::gil_scoped_release>())
         .def("build_triplets", &DeviceStore::build_triplets,
              py::call_guard<py::gil_scoped_release>())
         .def("gather_csr_padded", &DeviceStore::gather_csr_padded,

@@ -369,6 +369,29 @@ void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
                      const void* d_scratch, int out_t, bool coo, void* d_edge_out,
                      int32_t* d_shift_out, float* d_vec_out, bool nearest = false);
 
+// Cell-list path of the periodic fetch (docs/API.md, algorithm = "cells"): the
+// same rule, order and outputs bit for bit, through the grid of the open
+// cell-list path with a bin width per graph; real nodes only are binned, and
+// every dst probes the images of its box. radius_pbc_cells_count stands for
+// radius_pbc_count (d_edge_ptr and d_needed as it leaves them),
+// radius_pbc_cells_fill for radius_pbc_fill without the nearest mode.
+// d_scratch: radius_pbc_cells_scratch_bytes(nidx, ncap) bytes, under 112 *
+// ncap + 168 * nidx + 288 whatever the cells and coordinates are, 16-byte
+// aligned, no zeroing needed. Needs ncap + nidx < 2^31 and nodes * images <
+// 2^32 per graph, which the caller checks. Integer atomics place the nodes in
+// their bins; no floating-point atomics.
+size_t radius_pbc_cells_scratch_bytes(int64_t nidx, int64_t ncap);
+void radius_pbc_cells_count(hipStream_t stream, const void* d_pos, int pos_t,
+                            const void* d_cell, int cell_t, const int64_t* d_ptr,
+                            const int64_t* d_idx, int64_t nidx, int64_t nsamples,
+                            int64_t ncap, float r, int pbc, int max_shift, bool loop,
+                            void* d_scratch, int64_t* d_edge_ptr, int32_t* d_needed);
+void radius_pbc_cells_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                           const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                           int64_t ncap, int64_t ecap, float r, bool loop, void* d_scratch,
+                           int out_t, bool coo, void* d_edge_out, int32_t* d_shift_out,
+                           float* d_vec_out);
+
 // Triplet index of a radius-graph batch (DeviceStore::build_triplets). The
 // input is what radius_fill / radius_pbc_fill and graph_fill have written on
 // the same stream: d_edge_index the (2, ecap) ids of id_t (DDS_I64 or DDS_I32;

@@ -2694,31 +2694,42 @@ struct alignas(16) CellsNode {  // a node in bin order
     int32_t id;  // its row of the packed positions
 };
 
-// Bin width and the r2 = +inf case (see the section note).
+// Bin width and the r2 = +inf case (see the section note). The periodic path
+// has a width per graph, wg[s], instead of w.
 struct CellsBinning {
     double w;
     bool all;
+    const double* wg;
 };
 
+// floor(x / w) for a finite x, clamped.
+__device__ __forceinline__ int64_t cells_bin(double x, double w) {
+    double t = floor(x / w);
+    t = t < -kCellsClamp ? -kCellsClamp : (t > kCellsClamp ? kCellsClamp : t);
+    return (int64_t)t;
+}
+
 // The bin coordinate of one f32 coordinate; false for a node that has no bin.
-__device__ __forceinline__ bool cells_coord(float x, const CellsBinning& bn, int64_t& q) {
-    if (bn.all) {
+__device__ __forceinline__ bool cells_coord(float x, double w, bool all, int64_t& q) {
+    if (all) {
         q = 0;
         return x == x;
     }
     if (!(__builtin_fabsf(x) <= 3.402823466e+38f)) return false;
-    double t = floor((double)x / bn.w);
-    t = t < -kCellsClamp ? -kCellsClamp : (t > kCellsClamp ? kCellsClamp : t);
-    q = (int64_t)t;
+    q = cells_bin((double)x, w);
     return true;
 }
 
+// Packed row i of graph s.
 template <typename Tin>
 __device__ __forceinline__ bool cells_node_q(const Tin* __restrict__ pos, int64_t i,
-                                             const CellsBinning& bn, int64_t (&q)[3]) {
+                                             int64_t s, const CellsBinning& bn,
+                                             int64_t (&q)[3]) {
+    const double w = bn.wg ? bn.wg[s] : bn.w;
     bool ok = true;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) ok &= cells_coord(radius_coord(pos[3 * i + a]), bn, q[a]);
+    for (int a = 0; a < 3; ++a)
+        ok &= cells_coord(radius_coord(pos[3 * i + a]), w, bn.all, q[a]);
     return ok;
 }
 
@@ -2758,7 +2769,7 @@ k_cells_box(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr, int64_
         bool ok = false;
         if (i < ncap) {
             s = cells_graph_of(ptr, nidx, ncap, i);
-            if (s >= 0) ok = cells_node_q(pos, i, bn, q);
+            if (s >= 0) ok = cells_node_q(pos, i, s, bn, q);
         }
         const int64_t s0 = __shfl((long long)s, 0);
         if (__all(s == s0)) {
@@ -2830,7 +2841,7 @@ k_cells_hist(const Tin* __restrict__ pos, const int64_t* __restrict__ ptr, int64
         uint32_t b = kCellsNoBin;
         const int64_t s = cells_graph_of(ptr, nidx, ncap, i);
         int64_t q[3];
-        if (s >= 0 && cells_node_q(pos, i, bn, q)) {
+        if (s >= 0 && cells_node_q(pos, i, s, bn, q)) {
             const CellsGrid g = grid[s];
             int64_t c[3];
 #pragma unroll
@@ -2952,6 +2963,20 @@ __device__ __forceinline__ CellsDst cells_dst(const CellsNode* __restrict__ sort
     return d;
 }
 
+// Every node of the dst's rows of bins, in bin order: at(node).
+template <typename At>
+__device__ __forceinline__ void cells_rows(const CellsNode* __restrict__ sorted,
+                                           const int32_t* __restrict__ bin_start,
+                                           const CellsDst& d, At&& at) {
+    for (int32_t z = 0; z < d.nz; ++z) {
+        for (int32_t y = 0; y < d.ny; ++y) {
+            const int64_t row = d.row0 + ((int64_t)z * d.dimy + y) * d.dimx;
+            const int32_t end = bin_start[row + d.x1 + 1];
+            for (int32_t u = bin_start[row + d.x0]; u < end; ++u) at(sorted[u]);
+        }
+    }
+}
+
 // Every candidate of the dst that passes the rule: hit(id, dx, dy, dz), id the
 // source's packed row, in bin order.
 template <typename Hit>
@@ -2960,18 +2985,12 @@ __device__ __forceinline__ void cells_walk(const CellsNode* __restrict__ sorted,
                                            const CellsDst& d, float r2, bool loop,
                                            Hit&& hit) {
 #pragma clang fp contract(off)
-    for (int32_t z = 0; z < d.nz; ++z) {
-        for (int32_t y = 0; y < d.ny; ++y) {
-            const int64_t row = d.row0 + ((int64_t)z * d.dimy + y) * d.dimx;
-            const int32_t end = bin_start[row + d.x1 + 1];
-            for (int32_t u = bin_start[row + d.x0]; u < end; ++u) {
-                const CellsNode m = sorted[u];
-                const float dx = m.x - d.c.x, dy = m.y - d.c.y, dz = m.z - d.c.z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                if (d2 <= r2 && (loop || m.id != d.c.id)) hit(m.id, dx, dy, dz);
-            }
-        }
-    }
+    cells_rows(sorted, bin_start, d, [&](const CellsNode m) {
+#pragma clang fp contract(off)
+        const float dx = m.x - d.c.x, dy = m.y - d.c.y, dz = m.z - d.c.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 <= r2 && (loop || m.id != d.c.id)) hit(m.id, dx, dy, dz);
+    });
 }
 
 // deg[i] = min(neighbours of packed row i, kcap) for every node with a bin
@@ -3073,6 +3092,341 @@ k_cells_fill(const Tin* __restrict__ pos, const CellsNode* __restrict__ sorted,
                 }
             });
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Cell-list path of the periodic radius-graph fetch (algorithm = "cells" of
+// get_radius_graph_pbc_batch): the same edges, shifts, order and outputs as
+// k_radius_pbc_count / k_radius_pbc_fill, found in O(nodes x images probed) by
+// the grid of the open cell-list path, with one large cell spread over the
+// whole device. It stands where radius_pbc_count and radius_pbc_fill stand;
+// k_radius_scan and k_graph_fill are reused as they are, and so are
+// k_cells_init / box / grid / hist / scan_* / scatter / counts, which take a
+// bin width per graph here (CellsBinning::wg).
+//
+// Only real nodes are binned, no ghost atoms: scratch stays linear in Ncap + n
+// whatever the cells are. Images are met from the other side. A lane owns a
+// dst j, in bin order, and walks the images s of its graph's box in shift
+// order. For every image it forms t by the rule in float32 and the probe
+// p = x_j - t per axis in float64 (exact but for one rounding of 2^-53 |p|),
+// bins p with the graph's width and walks the nine rows of the probe's 27
+// bins, clipped to the grid. An image whose probe lies more than one bin
+// outside the graph's bin box on any axis holds no neighbour and is skipped:
+// with rel = q(p) - lo the test is -1 <= rel <= dim << sh, which is the test on
+// the unshifted bins (the box ends below lo + (dim << sh)) and implies the one
+// on the shifted bins, rel >> sh in -1 .. dim; the shift is arithmetic, so it
+// keeps neighbours neighbours for negative rel as well. For the zero image
+// nothing is added and the probe is x_j itself. Every candidate gets the
+// rule's own test and nothing else (pbc_cells_walk).
+//
+// Width, a superset of the rule's edges for every float32 input. With an
+// image, dx = fl(u + t_x) with u = fl(x_i - x_j) = (x_i - x_j)(1 + e1) and
+// dx = (u + t_x)(1 + e2), |e1|, |e2| <= 2^-24 (sums are exact where they are
+// subnormal; an overflow of either gives an infinite or NaN d2, which passes
+// only a +inf r2, see below). As on the open path a passing pair has |dx| <=
+// w0 (1 + 2^-23), w0 = max(r, 2^-62), so |u + t_x| <= w0 (1 + 2^-23)^2, and
+// |x_i - x_j| <= |u| (1 + 2^-23) <= (|t_x| + |u + t_x|)(1 + 2^-23). The real
+// distance of x_i from the real probe is |u + t_x - (x_i - x_j) e1|
+//   <= w0 (1 + 2^-23)^3 + 2^-24 (1 + 2^-23) |t_x| <= w0 (1 + 2^-21) + 2^-23 |t_x|:
+// the inner difference is rounded at the magnitude of t_x, not of r, so the
+// open width w0 (1 + 2^-10) holds only up to |t_x| of about 2^13 w0. The
+// graph's width is therefore
+//   w_g = w0 (1 + 2^-10) + 2^-22 T,  T = (1 + 2^-20) max_k sum_i b_i |a_ik|
+// in float64, an upper bound of every |t_k(s)| of the box (three roundings of
+// 2^-24; products that underflow add at most 2^-147, which vanishes in the
+// slack of the first term). (w0 (1 + 2^-21) + 2^-23 T) / w_g is a mediant of
+// (1 + 2^-21) / (1 + 2^-10) < 1 - 2^-11 and 1/2, so it is below 1 - 2^-11. The
+// quotients x_i / w_g and p / w_g carry 2^-53 relative each and p its own
+// rounding: for quotients up to 2^40 + 2 that is under 3 * 2^-13 in all, the
+// computed quotients are less than 1 apart and their floors differ by at most
+// 1. Beyond 2^40 + 2 the other quotient is beyond 2^40 + 1 and both floors are
+// clamped to the same bin; the clamp of the floors never widens a difference.
+// A non-finite T (an infinite cell entry on a searched axis) leaves the open
+// width: such a component makes t non-finite for every image, only the zero
+// image can hold an edge, and for it the open proof applies. A NaN entry is
+// ignored by the maximum for the same reason. A wider bin is always sound.
+//
+// Degenerate inputs. A zero-volume or non-finite cell has needed = INT32_MAX,
+// b = max_shift, and the walk is as above. An image with a NaN or infinite t
+// has no edge under a finite r2 (d2 is NaN or +inf) and is skipped. When r2
+// overflows to +inf every pair without a NaN passes, pairs with an infinite d2
+// included: the open path's single bin (`all`) holds every node without a NaN,
+// every image is probed there, and the rule's test decides.
+//
+// Edge order. A dst's run is ordered by shift, then src, and the lane takes
+// the images in shift order, so only the hits of one image need ordering, by
+// src. The fill keeps them in the private LDS column of the open fill
+// (kCellsSortMax ids per lane, column stride the block, 64 KiB per block) by
+// insertion and flushes the column at the end of every image to the dst's
+// running slot: edge_index, the image's edge_shift and edge_vec, recomputed
+// from the packed positions by the same float32 operations. An image with more
+// hits than a column ranks every hit by a second walk of that image only:
+// exact, quadratic in that image's hits. The count kernel does the same walk,
+// writes the degree (32 bits without a sign: nodes x images < 2^32 is the
+// caller's check) and uses no LDS. First slots come from the 64-bit scans of
+// the open path and per-graph totals from k_cells_counts. No float atomics;
+// no workgroup waits for another.
+//
+// Pipeline: k_cells_init, k_pbc_cells_box (per graph: PbcBox and
+// shifts_needed exactly as k_radius_pbc_count writes them, and w_g, which
+// lives next to the boxes and not in CellsGrid so that the open path's
+// scratch bound stands), k_cells_box / grid / hist / scan / scatter,
+// k_pbc_cells_count, scan, k_cells_counts, k_radius_scan; the fill is one
+// launch of k_pbc_cells_fill.
+//
+// Not done: a nearest cap on either cell path, a choice of algorithm per graph
+// inside one call, staging candidate rows in LDS, and a test on the unshifted
+// bins against the box's true upper end (the grid record keeps dim and sh).
+//
+// gfx950 (compiler remarks): k_pbc_cells_count 79 VGPRs, no LDS;
+// k_pbc_cells_fill 88..91 VGPRs, 64 KiB of LDS per block, two blocks per CU;
+// k_pbc_cells_box 40 VGPRs, no LDS; no kernel has scratch.
+//
+// Measured on MI355X (profiles/radius_pbc_cells_ab.txt), cubic cells at 4.5
+// atoms per unit volume, r = 1.0 (27 images), f32, int64 ids, exact
+// capacities, the whole fetch: one cell of 256 / 1 k / 4 k atoms 0.44 / 0.39 /
+// 0.44 ms against 4.8 / 73 / 1156 ms for the brute-force kernels; 16 k and
+// 64 k atoms 0.44 and 0.53 ms (brute force left out: seconds to minutes per
+// call); 64 cells of 2 k atoms 0.53 against 301 ms. Edge vectors add 2 to 5 %.
+// Both sides gave equal outputs on these random positions before they were
+// timed. The crossover is lower than the open call's and depends on the batch:
+// one cell alone is no slower on this path from 64 atoms, but 8,192 structures
+// of 2..64 atoms take 1.32 ms here against 0.99 ms, so it lies between 64 and
+// 256 atoms per structure. It was not located more closely and "auto" keeps
+// kCellsMinNodes, on its safe side; under "auto" that 8,192-structure shape
+// runs the brute-force kernels as before (992 against 993 us, within the
+// spread). Not measured: the per-kernel split, other densities, large
+// triclinic cells, f64, int32 ids and the ranking path.
+// ---------------------------------------------------------------------------
+
+// PbcBox, shifts_needed and the bin width of every request s, by
+// k_radius_pbc_count's kept test; a request that is not kept gets needed = 0,
+// an empty box and the open width.
+template <typename Tcell>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_pbc_cells_box(const Tcell* __restrict__ cell, const int64_t* __restrict__ ptr,
+                const int64_t* __restrict__ idx, int64_t nidx, int64_t nsamples,
+                int64_t ncap, float rf, double w_open, int pbc, int max_shift,
+                PbcBox* __restrict__ boxes, double* __restrict__ width,
+                int32_t* __restrict__ needed_out) {
+    const int64_t nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < nidx; s += nt) {
+        const int64_t p0 = ptr[s], p1 = ptr[s + 1], g = idx[s];
+        int needed[3] = {0, 0, 0};
+        PbcBox box = {};
+        double w = w_open;
+        if (g >= 0 && g < nsamples && p0 >= 0 && p1 <= ncap) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) box.a[k] = radius_coord(cell[9 * s + k]);
+            pbc_layers(box.a, rf, pbc, needed);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                box.b[k] = needed[k] < max_shift ? needed[k] : max_shift;
+            double T = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double m = ((double)box.b[0] * fabs((double)box.a[k]) +
+                                  (double)box.b[1] * fabs((double)box.a[3 + k])) +
+                                 (double)box.b[2] * fabs((double)box.a[6 + k]);
+                T = m > T ? m : T;  // a NaN is ignored
+            }
+            T *= 1.0 + 0x1p-20;
+            if (T <= 1.7976931348623157e308) w = w_open + 0x1p-22 * T;
+        }
+        boxes[s] = box;
+        width[s] = w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) needed_out[3 * s + k] = needed[k];
+    }
+}
+
+// Bins c0 .. c1 of one axis around the probe p (finite unless `all`); false
+// when no bin of the graph's box is the probe's bin or next to it.
+__device__ __forceinline__ bool pbc_cells_axis(double p, double w, bool all, int64_t lo,
+                                               int32_t sh, int32_t dim, int32_t& c0,
+                                               int32_t& c1) {
+    if (all) {
+        c0 = c1 = 0;
+        return true;
+    }
+    const int64_t rel = cells_bin(p, w) - lo;
+    if (rel < -1 || rel > ((int64_t)dim << sh)) return false;
+    const int32_t c = (int32_t)(rel >> sh);  // -1 .. dim
+    c0 = c > 0 ? c - 1 : 0;
+    c1 = c + 1 < dim ? c + 1 : dim - 1;
+    return true;
+}
+
+// Every image of dst c's box in shift order that can hold a neighbour:
+// img(s0, s1, s2, tx, ty, tz, zero, d), d the rows of bins to walk; g0 is the
+// graph's first bin.
+template <typename Img>
+__device__ __forceinline__ void pbc_cells_images(const CellsNode& c, const PbcBox& box,
+                                                 const CellsGrid& g, double w, bool all,
+                                                 int64_t g0, Img&& img) {
+#pragma clang fp contract(off)
+    for (int s0 = -box.b[0]; s0 <= box.b[0]; ++s0) {
+        for (int s1 = -box.b[1]; s1 <= box.b[1]; ++s1) {
+            for (int s2 = -box.b[2]; s2 <= box.b[2]; ++s2) {
+                const bool zero = (s0 | s1 | s2) == 0;
+                const float f0 = (float)s0, f1 = (float)s1, f2 = (float)s2;
+                const float tx = (f0 * box.a[0] + f1 * box.a[3]) + f2 * box.a[6];
+                const float ty = (f0 * box.a[1] + f1 * box.a[4]) + f2 * box.a[7];
+                const float tz = (f0 * box.a[2] + f1 * box.a[5]) + f2 * box.a[8];
+                const bool finite = __builtin_fabsf(tx) <= 3.402823466e+38f &&
+                                    __builtin_fabsf(ty) <= 3.402823466e+38f &&
+                                    __builtin_fabsf(tz) <= 3.402823466e+38f;
+                if (!zero && !all && !finite) continue;
+                const bool shifted = !zero && !all;  // `all` bins nothing
+                const double px = shifted ? (double)c.x - (double)tx : (double)c.x;
+                const double py = shifted ? (double)c.y - (double)ty : (double)c.y;
+                const double pz = shifted ? (double)c.z - (double)tz : (double)c.z;
+                CellsDst d;
+                int32_t y0, y1, z0, z1;
+                if (!pbc_cells_axis(px, w, all, g.lo[0], g.sh[0], g.dim[0], d.x0, d.x1) ||
+                    !pbc_cells_axis(py, w, all, g.lo[1], g.sh[1], g.dim[1], y0, y1) ||
+                    !pbc_cells_axis(pz, w, all, g.lo[2], g.sh[2], g.dim[2], z0, z1))
+                    continue;
+                d.c = c;
+                d.ny = y1 - y0 + 1;
+                d.nz = z1 - z0 + 1;
+                d.dimx = g.dim[0];
+                d.dimy = g.dim[1];
+                d.row0 = g0 + ((int64_t)z0 * g.dim[1] + y0) * g.dim[0];
+                img(s0, s1, s2, tx, ty, tz, zero, d);
+            }
+        }
+    }
+}
+
+// Every candidate of the rows d that passes the rule under the image t:
+// hit(id, dx, dy, dz), in bin order.
+template <typename Hit>
+__device__ __forceinline__ void pbc_cells_walk(const CellsNode* __restrict__ sorted,
+                                               const int32_t* __restrict__ bin_start,
+                                               const CellsDst& d, float tx, float ty,
+                                               float tz, bool zero, float r2, bool loop,
+                                               Hit&& hit) {
+#pragma clang fp contract(off)
+    cells_rows(sorted, bin_start, d, [&](const CellsNode m) {
+#pragma clang fp contract(off)
+        float dx = m.x - d.c.x, dy = m.y - d.c.y, dz = m.z - d.c.z;
+        if (!zero) {
+            dx = dx + tx;
+            dy = dy + ty;
+            dz = dz + tz;
+        }
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 <= r2 && (loop || !zero || m.id != d.c.id)) hit(m.id, dx, dy, dz);
+    });
+}
+
+// deg[i] = edges into packed row i, over every image, for every node with a
+// bin (the others keep k_cells_init's 0).
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_pbc_cells_count(const CellsNode* __restrict__ sorted,
+                  const int32_t* __restrict__ bin_start, const int32_t* __restrict__ total,
+                  const int64_t* __restrict__ ptr, int64_t nidx, int64_t ncap,
+                  const CellsGrid* __restrict__ grid, const PbcBox* __restrict__ boxes,
+                  const double* __restrict__ width, float r2, bool all, bool loop,
+                  uint32_t* __restrict__ deg) {
+    const int64_t m = *total, nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < m; t += nt) {
+        const CellsNode c = sorted[t];
+        const int64_t s = cells_graph_of(ptr, nidx, ncap, c.id);  // kept: it has a bin
+        uint32_t cnt = 0;
+        pbc_cells_images(c, boxes[s], grid[s], width[s], all, ptr[s] + s,
+                         [&](int, int, int, float tx, float ty, float tz, bool zero,
+                             const CellsDst& d) {
+                             pbc_cells_walk(sorted, bin_start, d, tx, ty, tz, zero, r2, loop,
+                                            [&](int32_t, float, float, float) { ++cnt; });
+                         });
+        deg[c.id] = cnt;
+    }
+}
+
+// The edges of every graph k_radius_pbc_fill would write, in its layout: dst
+// `i`'s run starts at off[i], image after image, sources ascending inside an
+// image. See the section note for the two orderings.
+template <typename Tin, typename Tout, bool COO, bool VEC>
+__global__ void DDS_NO_PK_F32 __launch_bounds__(kBlock)
+k_pbc_cells_fill(const Tin* __restrict__ pos, const CellsNode* __restrict__ sorted,
+                 const int32_t* __restrict__ bin_start, const int32_t* __restrict__ total,
+                 const int64_t* __restrict__ ptr, const int64_t* __restrict__ edge_ptr,
+                 int64_t nidx, int64_t ncap, int64_t ecap,
+                 const CellsGrid* __restrict__ grid, const PbcBox* __restrict__ boxes,
+                 const double* __restrict__ width, const int64_t* __restrict__ off, float r2,
+                 bool all, bool loop, Tout* __restrict__ out, int32_t* __restrict__ shift,
+                 float* __restrict__ vec) {
+#pragma clang fp contract(off)
+    __shared__ int32_t s_ids[kCellsSortMax * kBlock];
+    int32_t* col = s_ids + threadIdx.x;  // entry k at col[k * kBlock]
+    const int64_t m = *total, nt = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < m; t += nt) {
+        const CellsNode c = sorted[t];
+        const int32_t i = c.id;
+        int64_t o = off[i];  // the dst's running slot
+        if (off[i + 1] - o <= 0) continue;
+        const int64_t s = cells_graph_of(ptr, nidx, ncap, i);
+        if (edge_ptr[s + 1] > ecap || o < 0) continue;  // this graph's edges are not kept
+        pbc_cells_images(
+            c, boxes[s], grid[s], width[s], all, ptr[s] + s,
+            [&](int s0, int s1, int s2, float tx, float ty, float tz, bool zero,
+                const CellsDst& d) {
+#pragma clang fp contract(off)
+                auto put = [&](int64_t at, int64_t src, float dx, float dy, float dz) {
+                    cells_store<Tout, COO>(out, ecap, at, src, i);
+                    shift[3 * at] = s0;
+                    shift[3 * at + 1] = s1;
+                    shift[3 * at + 2] = s2;
+                    if constexpr (VEC) {
+                        vec[3 * at] = dx;
+                        vec[3 * at + 1] = dy;
+                        vec[3 * at + 2] = dz;
+                    }
+                };
+                int h = 0;  // hits of this image; the column keeps the first kCellsSortMax
+                pbc_cells_walk(sorted, bin_start, d, tx, ty, tz, zero, r2, loop,
+                               [&](int32_t id, float, float, float) {
+                                   if (h < kCellsSortMax) {
+                                       int p = h;
+                                       for (; p > 0 && col[(p - 1) * kBlock] > id; --p)
+                                           col[p * kBlock] = col[(p - 1) * kBlock];
+                                       col[p * kBlock] = id;
+                                   }
+                                   ++h;
+                               });
+                if (h <= kCellsSortMax) {
+                    for (int k = 0; k < h; ++k) {
+                        const int64_t src = col[k * kBlock];
+                        float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+                        if constexpr (VEC) {
+                            dx = radius_coord(pos[3 * src]) - c.x;
+                            dy = radius_coord(pos[3 * src + 1]) - c.y;
+                            dz = radius_coord(pos[3 * src + 2]) - c.z;
+                            if (!zero) {
+                                dx = dx + tx;
+                                dy = dy + ty;
+                                dz = dz + tz;
+                            }
+                        }
+                        put(o + k, src, dx, dy, dz);
+                    }
+                } else {
+                    pbc_cells_walk(sorted, bin_start, d, tx, ty, tz, zero, r2, loop,
+                                   [&](int32_t id, float dx, float dy, float dz) {
+                                       int64_t rank = 0;
+                                       pbc_cells_walk(sorted, bin_start, d, tx, ty, tz, zero,
+                                                      r2, loop,
+                                                      [&](int32_t other, float, float, float) {
+                                                          rank += other < id;
+                                                      });
+                                       put(o + rank, id, dx, dy, dz);
+                                   });
+                }
+                o += h;
+            });
     }
 }
 
@@ -4037,11 +4391,13 @@ struct CellsScratch {
     uint32_t* bin_of;    // [ncap]
     uint32_t* slot;      // [ncap]
     int32_t* bins;       // [nbins + 1], counts and then starts
+    PbcBox* boxes;       // [nidx], the periodic path only
+    double* width;       // [nidx], likewise
     int64_t nbins;
     size_t bytes;
 };
 
-CellsScratch cells_scratch(void* base, int64_t nidx, int64_t ncap) {
+CellsScratch cells_scratch(void* base, int64_t nidx, int64_t ncap, bool pbc = false) {
     CellsScratch s;
     s.nbins = ncap + nidx;
     char* p = reinterpret_cast<char*>(base);
@@ -4060,6 +4416,8 @@ CellsScratch cells_scratch(void* base, int64_t nidx, int64_t ncap) {
     take(s.bin_of, ncap);
     take(s.slot, ncap);
     take(s.bins, s.nbins + 1);
+    take(s.boxes, pbc ? nidx : 0);
+    take(s.width, pbc ? nidx : 0);
     s.bytes = (size_t)(p - reinterpret_cast<char*>(base));
     return s;
 }
@@ -4096,7 +4454,7 @@ void radius_cells_count(hipStream_t stream, const void* d_pos, int pos_t,
     const CellsScratch sc = cells_scratch(d_scratch, nidx, ncap);
     const float r2 = r * r;
     const double w0 = (double)r > 0x1p-62 ? (double)r : 0x1p-62;
-    const CellsBinning bn = {w0 * (1.0 + 0x1p-10), std::isinf(r2)};
+    const CellsBinning bn = {w0 * (1.0 + 0x1p-10), std::isinf(r2), nullptr};
     const int kcap = max_neighbors > 0 && max_neighbors < INT32_MAX
                          ? (int)max_neighbors : INT32_MAX;
     const int by_node = cells_blocks(ncap), by_graph = cells_blocks(nidx);
@@ -4281,6 +4639,96 @@ void radius_pbc_fill(hipStream_t stream, const void* d_pos, int pos_t,
         if (pos_t == DDS_F64) launch_out(TypeTag<double>{}, G);
         else if (pos_t == DDS_F32) launch_out(TypeTag<float>{}, G);
     });
+}
+
+// The open cell-list scratch, then 48 bytes (PbcBox) and 8 (the bin width) per
+// graph, each part rounded up to 16: under 112 * ncap + 168 * nidx + 288.
+size_t radius_pbc_cells_scratch_bytes(int64_t nidx, int64_t ncap) {
+    return cells_scratch(nullptr, nidx, ncap, true).bytes;
+}
+
+void radius_pbc_cells_count(hipStream_t stream, const void* d_pos, int pos_t,
+                            const void* d_cell, int cell_t, const int64_t* d_ptr,
+                            const int64_t* d_idx, int64_t nidx, int64_t nsamples,
+                            int64_t ncap, float r, int pbc, int max_shift, bool loop,
+                            void* d_scratch, int64_t* d_edge_ptr, int32_t* d_needed) {
+    if (nidx == 0 || (pos_t != DDS_F32 && pos_t != DDS_F64) ||
+        (cell_t != DDS_F32 && cell_t != DDS_F64))
+        return;
+    const CellsScratch sc = cells_scratch(d_scratch, nidx, ncap, true);
+    const float r2 = r * r;
+    const bool all = std::isinf(r2);
+    const double w0 = (double)r > 0x1p-62 ? (double)r : 0x1p-62;
+    const double w_open = w0 * (1.0 + 0x1p-10);
+    const CellsBinning bn = {w_open, all, sc.width};
+    const int by_node = cells_blocks(ncap), by_graph = cells_blocks(nidx);
+    hipLaunchKernelGGL(k_cells_init, dim3(cells_blocks(sc.nbins + 1)), dim3(kBlock), 0,
+                       stream, nidx, ncap, sc.nbins, sc.box, sc.deg, sc.bins);
+    auto boxes = [&](auto tc) {
+        using Tcell = typename decltype(tc)::type;
+        hipLaunchKernelGGL((k_pbc_cells_box<Tcell>), dim3(by_graph), dim3(kBlock), 0, stream,
+                           (const Tcell*)d_cell, d_ptr, d_idx, nidx, nsamples, ncap, r,
+                           w_open, pbc, max_shift, sc.boxes, sc.width, d_needed);
+    };
+    if (cell_t == DDS_F64) boxes(TypeTag<double>{});
+    else boxes(TypeTag<float>{});
+    auto typed = [&](auto ti) {
+        using Tin = typename decltype(ti)::type;
+        const Tin* pos = (const Tin*)d_pos;
+        hipLaunchKernelGGL((k_cells_box<Tin>), dim3(by_node), dim3(kBlock), 0, stream, pos,
+                           d_ptr, nidx, ncap, bn, sc.box);
+        hipLaunchKernelGGL(k_cells_grid, dim3(by_graph), dim3(kBlock), 0, stream, d_ptr,
+                           nidx, ncap, sc.box, sc.grid);
+        hipLaunchKernelGGL((k_cells_hist<Tin>), dim3(by_node), dim3(kBlock), 0, stream, pos,
+                           d_ptr, nidx, ncap, bn, sc.grid, sc.bin_of, sc.slot, sc.bins);
+        cells_scan<int32_t, int32_t>(stream, sc.bins, sc.nbins + 1, sc.sums, sc.bins);
+        hipLaunchKernelGGL((k_cells_scatter<Tin>), dim3(by_node), dim3(kBlock), 0, stream,
+                           pos, ncap, sc.bin_of, sc.slot, sc.bins, sc.sorted);
+    };
+    if (pos_t == DDS_F64) typed(TypeTag<double>{});
+    else typed(TypeTag<float>{});
+    uint32_t* deg = reinterpret_cast<uint32_t*>(sc.deg);
+    hipLaunchKernelGGL(k_pbc_cells_count, dim3(by_node), dim3(kBlock), 0, stream, sc.sorted,
+                       sc.bins, sc.bins + sc.nbins, d_ptr, nidx, ncap, sc.grid, sc.boxes,
+                       sc.width, r2, all, loop, deg);
+    cells_scan<uint32_t, int64_t>(stream, deg, ncap + 1, sc.sums, sc.off);
+    hipLaunchKernelGGL(k_cells_counts, dim3(by_graph), dim3(kBlock), 0, stream, d_ptr, nidx,
+                       ncap, sc.off, sc.counts);
+    hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(kBlock), 0, stream, sc.counts, nidx,
+                       d_edge_ptr);
+}
+
+void radius_pbc_cells_fill(hipStream_t stream, const void* d_pos, int pos_t,
+                           const int64_t* d_ptr, const int64_t* d_edge_ptr, int64_t nidx,
+                           int64_t ncap, int64_t ecap, float r, bool loop, void* d_scratch,
+                           int out_t, bool coo, void* d_edge_out, int32_t* d_shift_out,
+                           float* d_vec_out) {
+    if (nidx == 0 || ecap == 0 || ncap == 0) return;
+    const CellsScratch sc = cells_scratch(d_scratch, nidx, ncap, true);
+    const float r2 = r * r;
+    const int grid = cells_blocks(ncap);
+    auto launch = [&](auto ti, auto to, auto c, auto v) {
+        using Tin = typename decltype(ti)::type;
+        using Tout = typename decltype(to)::type;
+        hipLaunchKernelGGL(
+            (k_pbc_cells_fill<Tin, Tout, decltype(c)::value, decltype(v)::value>),
+            dim3(grid), dim3(kBlock), 0, stream, (const Tin*)d_pos, sc.sorted, sc.bins,
+            sc.bins + sc.nbins, d_ptr, d_edge_ptr, nidx, ncap, ecap, sc.grid, sc.boxes,
+            sc.width, sc.off, r2, std::isinf(r2), loop, (Tout*)d_edge_out, d_shift_out,
+            d_vec_out);
+    };
+    auto launch_flags = [&](auto ti, auto to) {
+        if (coo && d_vec_out) launch(ti, to, std::true_type{}, std::true_type{});
+        else if (coo) launch(ti, to, std::true_type{}, std::false_type{});
+        else if (d_vec_out) launch(ti, to, std::false_type{}, std::true_type{});
+        else launch(ti, to, std::false_type{}, std::false_type{});
+    };
+    auto launch_out = [&](auto ti) {
+        if (out_t == DDS_I64) launch_flags(ti, TypeTag<int64_t>{});
+        else if (out_t == DDS_I32) launch_flags(ti, TypeTag<int32_t>{});
+    };
+    if (pos_t == DDS_F64) launch_out(TypeTag<double>{});
+    else if (pos_t == DDS_F32) launch_out(TypeTag<float>{});
 }
 
 int triplet_slice() { return kTripletSlice; }

@@ -1425,15 +1425,20 @@ class DDStore:
             raise ValueError(
                 f"ddstore {what}: the nearest cap needs max_neighbors, an int in "
                 f"1..{_C.RADIUS_NEAREST_MAX}")
+        if not self._images_fit(name, images):
+            raise ValueError(
+                f"ddstore {what}: the nearest cap ranks at most 2**32 - 1 candidates "
+                "(nodes x images) per dst")
+
+    def _images_fit(self, name, images):
+        """Whether the variable's largest sample times ``images`` is under
+        ``2**32``: from the host offsets, once per variable and image count."""
         key = (name, "nearest", images)
         if key not in self._graph_extras_ok:
             goff = self._meta(name)["goff"]
             most = int((goff[1:] - goff[:-1]).max()) if goff.numel() > 1 else 0
             self._graph_extras_ok[key] = most * images < 2 ** 32
-        if not self._graph_extras_ok[key]:
-            raise ValueError(
-                f"ddstore {what}: the nearest cap ranks at most 2**32 - 1 candidates "
-                "(nodes x images) per dst")
+        return self._graph_extras_ok[key]
 
     @staticmethod
     def _thin_nearest(m: torch.Tensor, d2: torch.Tensor, k: int) -> torch.Tensor:
@@ -1528,6 +1533,7 @@ class DDStore:
         edge_fill: int = -1,
         edge_vec: bool = False,
         node_extras: Sequence[str] = (),
+        algorithm: str = "auto",
     ) -> PeriodicGraphBatch:
         """:meth:`get_radius_graph_batch` for periodic structures: the
         neighbours of a node include the translated images of the other nodes
@@ -1606,8 +1612,29 @@ class DDStore:
         Positions outside the cell are legal, but images beyond the box are
         not searched: wrap first. ``shift_out`` (``3 * Ecap`` int32) joins
         ``pos_out``, ``edge_out`` and ``batch_out`` (and ``vec_out`` with
-        ``edge_vec=True``): all or none."""
+        ``edge_vec=True``): all or none.
+
+        ``algorithm`` (``"auto"``, ``"brute"`` or ``"cells"``, anything else:
+        ``ValueError``) is that of :meth:`get_radius_graph_batch`; every field
+        and counter is the same bit for bit. ``"brute"`` tests every (dst,
+        image, src) triple of a graph on one lane group. ``"cells"`` bins the
+        graph's real nodes into a spatial grid with a bin width of its own
+        per graph and lets every node probe the images of its box, skipping
+        those that lie outside the grid; it has no nearest cap
+        (``max_neighbors``: ``ValueError``), needs ``Ncap + n < 2**31`` and
+        refuses (``ValueError``) a variable whose largest sample has ``nodes *
+        (2*max_shift+1)**3 >= 2**32``. ``"auto"`` takes ``"cells"`` iff
+        ``max_neighbors is None``, the largest sample has at least
+        ``_C.RADIUS_CELLS_MIN_NODES`` nodes and passes that product check,
+        else ``"brute"``; the choice is per call, from the host offsets, no
+        sync. The host backend checks the argument and ignores it."""
         what = "get_radius_graph_pbc_batch"
+        if algorithm not in ("auto", "brute", "cells"):
+            raise ValueError(
+                f"ddstore {what}: algorithm must be 'auto', 'brute' or 'cells'")
+        if algorithm == "cells" and max_neighbors is not None:
+            raise ValueError(
+                f"ddstore {what}: algorithm='cells' has no nearest cap (max_neighbors)")
         self._refuse_mx(what, pos_name)
         meta = self._meta(pos_name)
         if (not meta["is_csr"] or meta["disp"] != 3
@@ -1640,6 +1667,14 @@ class DDStore:
             self._check_nearest(what, max_neighbors, pos_name,
                                 (2 * int(max_shift) + 1) ** 3)
         k = int(max_neighbors) if max_neighbors is not None else 0
+        cells = False
+        if algorithm != "brute" and max_neighbors is None:
+            fit = self._images_fit(pos_name, (2 * int(max_shift) + 1) ** 3)
+            if algorithm == "cells" and not fit:
+                raise ValueError(
+                    f"ddstore {what}: algorithm='cells' counts at most 2**32 - 1 "
+                    "candidates (nodes x images) per dst")
+            cells = fit and (algorithm == "cells" or self._cells_by_size(pos_name))
         if edge_dtype not in (torch.int32, torch.int64):
             raise TypeError(f"ddstore {what}: edge_dtype must be int32 or int64")
         for nm in node_extras:
@@ -1692,7 +1727,7 @@ class DDStore:
                 self._backend.gather_radius_graph_pbc(
                     pos_name, cell_name, idx, float(rf), mask, int(max_shift),
                     bool(loop), pos_out, edge_out, batch_out, shift_out, vec_out,
-                    bool(edge_vec), sized, bool(coo), fill, k))
+                    bool(edge_vec), sized, bool(coo), fill, k, cells))
         else:
             ptr, edge_ptr, edge_out, shift_out, vec_out, cell, needed = (
                 self._radius_graph_pbc_host(
